@@ -22,7 +22,18 @@ before the timed region.
 Each rank generates only its row group's edges and its column slice of X (metric.Shard).
 Total work is fixed (one Reddit graph): "scaling": "strong"; value = E / max-rank step time.
 
-Printed JSON (rank 0):
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) builds the inputs, warms up, times the K steps
+and prints the headline line: metric, value, unit, ms_per_step, dtype, config.  Nothing else runs.
+  --dump-outputs DIR  after the timed steps, what the last timed step left in the output table a caller
+                of the aggregate receives: DIR/y.npy (one GPU; DIR/y_rank<r>.npy per rank at N > 1), fp32.
+                A table over the 48 MiB budget (shared by the ranks) is written as a fixed row sample
+                (numpy default_rng(0), sorted, the same rows every run); the inputs are a function of
+                (seed, id) alone, so two builds run with the same arguments see identical inputs.
+  --full        everything below besides the headline: the PMC passes, kernel-only and per-kernel times,
+                the oracle parity, the BASELINE-config layers and the CPU baseline (--no-pmc,
+                --no-cpu-baseline and --layers none still drop single legs).
+
+Printed JSON with --full (rank 0), beside the headline fields:
   parity        sampled output rows of every rank (incl. the heaviest and lightest) re-derived in fp64
                 by the oracle (oracle/isa_ref.aggregate), |err| <= 1e-5 * sum|terms| + 1e-6 each
   roofline      the aggregate launch pair (k_agg_h32 + k_seg_reduce) of every rank's tile: traffic = memory-side
@@ -69,6 +80,7 @@ PEAK_HBM_GBS = 8000.0     # MI355X_MICROARCH.md chip table (spec)
 L2_GATHER_GBS = 18800.0   # MI355X_MICROARCH.md §Indexed rows: rows shared by every workgroup (L2), chip-wide
 METRIC_NAME = "edges/sec + achieved HBM GB/s, GAT aggregate on Reddit, 1/2/4/8 MI355X"
 CALIB_ROWS = 1 << 21      # known-byte gather for the FETCH_SIZE calibration: 2 M rows x 512 B = 1 GiB table
+DUMP_BYTES = 48 << 20     # --dump-outputs: budget of all the .npy files of one run
 
 
 def log(rank, msg):
@@ -545,6 +557,82 @@ def rank_roofline(per_rank, peak=PEAK_HBM_GBS):
             "per_rank": rows}
 
 
+def kernel_times(agg, dev, steps):
+    """--full: (kernel-only ms of one step's launches, {phase: ms} or None), HIP events on the
+    launch stream, for the roofline."""
+    stream = torch.cuda.current_stream(dev)
+    n_evt = min(max(steps, 1), 10)
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_evt)]
+    for a, b in evs:
+        a.record(stream)
+        for c in range(len(agg.parts)):
+            agg.launch(c)
+        b.record(stream)
+    torch.cuda.synchronize()
+    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+    # the same launches split by phase (knob seg_phase: 1 = the gather items only, 2 = the ordered
+    # reduce only, reading the slabs the items just wrote): per-kernel times for the roofline
+    phase_ms = None
+    if agg.impl == "blocked":
+        pev = {1: [], 2: []}
+        try:
+            for _ in range(n_evt):
+                for ph in (1, 2):
+                    ops.set_debug("seg_phase", ph)
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(stream)
+                    for c in range(len(agg.parts)):
+                        agg.launch(c)
+                    b.record(stream)
+                    pev[ph].append((a, b))
+        finally:
+            ops.set_debug("seg_phase", 0)
+        torch.cuda.synchronize()
+        phase_ms = {ph: float(np.mean([a.elapsed_time(b) for a, b in v])) for ph, v in pev.items()}
+    return kern_ms, phase_ms
+
+
+def headline(args, world, mode, pr, pc, chunks, shard, agg, value, ms_per_step):
+    """The result line of a plain run; --full adds its legs to it."""
+    if mode == "single":
+        par = "one GPU, whole graph"
+    elif mode == "edges":
+        par = (f"edge partition: {pr}x{pc} grid of row-group x source-column tiles (tile-metadata nnz cuts), "
+               f"RCCL reduce-scatter of partial vertex aggregates in each row group, {chunks} overlapped row chunks")
+    else:
+        par = f"destination-row tiles x{pr} + RCCL all-gather of Y, {chunks} overlapped row chunks"
+    return {
+        "metric": METRIC_NAME, "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
+        "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic, counter-hashed: lognormal-degree CSR (mean deg 492), uniform sources, X~N(0,1), "
+                "alpha=per-head softmax over in-edges of N(0,1) logits",
+        "config": {"workload": "GAT layer-1 aggregate block [3,11,12] (scatter C -> applyedge MUL -> gather ADD)",
+                   "graph": "reddit-shaped", "N": args.n, "E": args.e, "F": F, "heads": HEADS,
+                   "parallelism": par, "mode": mode, "grid": f"{pr}x{pc}", "row_chunks": chunks,
+                   "chunk_rows": shard.grid.mks if mode == "edges" else None,
+                   "impl": agg.impl, "blocks": agg.blocks if agg.impl == "blocked" else None,
+                   "world_size_seen": dist.get_world_size() if world > 1 else 1,
+                   "backend": (dist.get_backend() if world > 1 else None)},
+    }
+
+
+def dump_outputs(out_dir, agg, mode, world, rank):
+    """--dump-outputs: the table a caller of the timed path receives, as the last timed step left it
+    (one GPU and edges mode: this rank's complete rows of Y; rows mode at N > 1: the all-gathered
+    padded table), fp32.  The run's files share DUMP_BYTES: a larger table is written as a row
+    sample drawn once from numpy's default_rng(0), sorted -- the same rows for the same arguments."""
+    t = agg.y_full if mode == "rows" and world > 1 else agg.y_own
+    keep = (DUMP_BYTES // world - 4096) // (t.shape[1] * 4)   # 4096: room for the .npy header
+    if t.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(0).choice(t.shape[0], keep, replace=False))
+        t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+    os.makedirs(out_dir, exist_ok=True)
+    name = "y.npy" if world == 1 else f"y_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), t.cpu().numpy().astype(np.float32, copy=False))
+    return name, tuple(t.shape)
+
+
 # ----------------------------------------------------------------------------------------------
 def main():
     if os.environ.get("GTA_STALL_DUMP"):  # diagnostics: every rank prints its Python stack every S seconds
@@ -554,6 +642,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: PMC traffic passes, kernel-only / per-kernel times and the roofline, "
+                         "fp64 oracle parity, the BASELINE-config layers, the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the output table of the last timed step to DIR/y.npy (fp32; a fixed row sample "
+                         "when it is larger than 48 MiB; y_rank<r>.npy per rank at N > 1)")
     ap.add_argument("--mode", choices=["edges", "rows"], default="edges",
                     help="N>1: edges = 2-D edge tiles + RCCL reduce-scatter of partial aggregates (north star); "
                          "rows = destination-row tiles + RCCL all-gather of Y")
@@ -599,7 +693,7 @@ def main():
 
     # PMC passes first: child processes on this rank's own tile, before this process initialises the GPU
     pmc = None
-    if not args.no_pmc:
+    if args.full and not args.no_pmc:
         log(rank, "rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) on this rank's kernels")
         if args.pmc_dir:
             keep = args.pmc_dir if world == 1 else os.path.join(args.pmc_dir, f"rank{rank}")
@@ -636,37 +730,7 @@ def main():
     if world > 1:
         dist.barrier()
     log(rank, "warmup done, timing")
-
-    # kernel-only timing (HIP events on the launch stream) for the roofline
-    stream = torch.cuda.current_stream(dev)
-    n_evt = min(max(args.steps, 1), 10)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_evt)]
-    for a, b in evs:
-        a.record(stream)
-        for c in range(len(agg.parts)):
-            agg.launch(c)
-        b.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-    # the same launches split by phase (knob seg_phase: 1 = the gather items only, 2 = the ordered
-    # reduce only, reading the slabs the items just wrote): per-kernel times for the roofline
-    phase_ms = None
-    if agg.impl == "blocked":
-        pev = {1: [], 2: []}
-        try:
-            for _ in range(n_evt):
-                for ph in (1, 2):
-                    ops.set_debug("seg_phase", ph)
-                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    a.record(stream)
-                    for c in range(len(agg.parts)):
-                        agg.launch(c)
-                    b.record(stream)
-                    pev[ph].append((a, b))
-        finally:
-            ops.set_debug("seg_phase", 0)
-        torch.cuda.synchronize()
-        phase_ms = {ph: float(np.mean([a.elapsed_time(b) for a, b in v])) for ph, v in pev.items()}
+    kern_ms, phase_ms = kernel_times(agg, dev, args.steps) if args.full else (None, None)
 
     # timed region: K steps, barrier + sync on both sides, max over ranks
     if world > 1:
@@ -686,7 +750,18 @@ def main():
         dt = float(t.item())
     ms_per_step = dt * 1e3 / args.steps
     value = args.e / (ms_per_step / 1e3)
-    log(rank, f"timed: {ms_per_step:.3f} ms/step (own {own_ms:.3f}, kernels alone {kern_ms:.3f})")
+    log(rank, f"timed: {ms_per_step:.3f} ms/step (own {own_ms:.3f}"
+              + (f", kernels alone {kern_ms:.3f})" if args.full else ")"))
+    if args.dump_outputs:
+        log(rank, "wrote %s %s" % dump_outputs(args.dump_outputs, agg, mode, world, rank))
+    result = headline(args, world, mode, pr, pc, chunks, shard, agg, value, ms_per_step)
+    if not args.full:  # the plain run ends here
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
 
     # parity: this rank's own output rows (complete sums after the exchange) vs the fp64 oracle
     agg.step()
@@ -765,30 +840,7 @@ def main():
                            "frac": byt / (phase_ms[ph] / 1e3) / 1e9 / PEAK_HBM_GBS}
                     for name, ph, byt in (("k_agg_h32", 1, pmc["agg_bytes"]), ("k_seg_reduce", 2, pmc["reduce_bytes"]))}
 
-    if mode == "single":
-        par = "one GPU, whole graph"
-    elif mode == "edges":
-        par = (f"edge partition: {pr}x{pc} grid of row-group x source-column tiles (tile-metadata nnz cuts), "
-               f"RCCL reduce-scatter of partial vertex aggregates in each row group, {chunks} overlapped row chunks")
-    else:
-        par = f"destination-row tiles x{pr} + RCCL all-gather of Y, {chunks} overlapped row chunks"
-    result = {
-        "metric": METRIC_NAME, "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
-        "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic, counter-hashed: lognormal-degree CSR (mean deg 492), uniform sources, X~N(0,1), "
-                "alpha=per-head softmax over in-edges of N(0,1) logits",
-        "config": {"workload": "GAT layer-1 aggregate block [3,11,12] (scatter C -> applyedge MUL -> gather ADD)",
-                   "graph": "reddit-shaped", "N": args.n, "E": args.e, "F": F, "heads": HEADS,
-                   "parallelism": par, "mode": mode, "grid": f"{pr}x{pc}", "row_chunks": chunks,
-                   "chunk_rows": shard.grid.mks if mode == "edges" else None,
-                   "impl": agg.impl, "blocks": agg.blocks if agg.impl == "blocked" else None,
-                   "world_size_seen": dist.get_world_size() if world > 1 else 1,
-                   "backend": (dist.get_backend() if world > 1 else None)},
-        "achieved_GBps": roof["achieved"],
-        "parity": parity,
-        "roofline": roof,
-    }
+    result.update({"achieved_GBps": roof["achieved"], "parity": parity, "roofline": roof})
     # whole BASELINE-config layers at the same N (configs #4 / #5: GraphSAGE Reddit, GIN products), every
     # rank, after the metric (secondary numbers: the metric above is the headline)
     if args.layers and args.layers != "none":

@@ -62,7 +62,7 @@ def test_two_rank_sage_reddit_full_size():
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["edges", "rows"])
 def test_two_rank_bench_full_size(mode):
-    """bench.py --gpus 2 at the full metric size, both ranks on one GPU over gloo (RCCL cannot
+    """bench.py --gpus 2 --full at the full metric size, both ranks on one GPU over gloo (RCCL cannot
     put two ranks on one device): each rank generates only its shard, the exchange runs, and every
     rank's sampled output rows match the fp64 oracle (the bench's own parity field).  The N > 1 line
     carries what the N = 1 line does: each rank's own PMC bytes (its child rebuilt the
@@ -72,7 +72,7 @@ def test_two_rank_bench_full_size(mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mode", mode,
-           "--parity-rows", "128", "--cpu-baseline-s", "3", "--layers", "gcn-cora"]
+           "--full", "--parity-rows", "128", "--cpu-baseline-s", "3", "--layers", "gcn-cora"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=170)
     assert r.returncode == 0, r.stderr[-3000:]
     rec = [json.loads(line) for line in r.stdout.splitlines() if line.startswith("{")][-1]
