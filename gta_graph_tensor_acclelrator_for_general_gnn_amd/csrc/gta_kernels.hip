@@ -4360,7 +4360,10 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
 #undef GTA_LEAN
     ok = true;
   }
-  if (!ok && ex && tuning().expr_lean && lpe == kWave && nv == 1 && (vw == 2 || vw == 4)) {
+  // k_agg_expr masks no column: only rows that exactly fill the wave (F = 128 at VW 2, 256 at VW 4).
+  // lpe == kWave alone also holds for 33..63 lanes (F = 66..126 at VW 2, 132..252 at VW 4), whose
+  // idle lanes would load and store past column F: those widths take k_aggregate's XM_EX* form
+  if (!ok && ex && tuning().expr_lean && lpe == kWave && nv == 1 && (vw == 2 || vw == 4) && F == kWave * vw) {
     const int64_t blocks = (bound + kWavesPerBlock - 1) / kWavesPerBlock;
     const dim3 grid(static_cast<unsigned>(blocks)), blk(kBlock);
 #define GTA_EXPR(VW_, XM_)                                                                                   \
