@@ -50,6 +50,8 @@ def parser():
     p.add_argument("--layers", default="1,2,3", help="genGraphOP layers to run (default 1,2,3)")
     p.add_argument("--feature", type=int, default=None, help="input width (default: the dataset's)")
     p.add_argument("--heads", type=int, default=16, help="attention heads (GAT)")
+    p.add_argument("--aggregator", default="ADD", choices=list(frontend.AGGREGATORS),
+                   help="reduce function of the message gathers (their COMP_TYPE); GAT takes ADD only")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--reps", type=int, default=3, help="runs per layer; the fastest is reported")
     p.add_argument("--model-edges", type=int, default=1 << 20,
@@ -69,10 +71,11 @@ def run(args, device, log=print):
     layers = []
     meta = tiles.metadata(g, start=64, end=min(g.n_rows, 4096))  # what pipeline.Layer computes by default
     for L in layer_ids:
-        records = frontend.gen_ops(args.network, L, g.n_rows, g.nnz, feature, args.isReorder, args.heads)
+        records = frontend.gen_ops(args.network, L, g.n_rows, g.nnz, feature, args.isReorder, args.heads,
+                                   getattr(args, "aggregator", "ADD"))
         cands = compiler.search(records, g.n_rows, *meta, pingpang=args.isPingpang, sinput=args.isSinput)
         kw = dict(reorder=args.isReorder, heads=args.heads, metadata=meta, pingpang=args.isPingpang,
-                  sinput=args.isSinput)
+                  sinput=args.isSinput, aggregator=getattr(args, "aggregator", "ADD"))
         lay = None
         for k, (op_array, tile_size_list) in enumerate(c[:2] for c in cands):
             try:

@@ -581,6 +581,156 @@ k_aggregate(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indi
 }
 
 // ---------------------------------------------------------------------------
+// K2' reduce: the gather whose COMP_TYPE is MAX or MIN (gta_reduce).
+//   k_aggregate's generic form -- one wavefront per work item, LPE lanes per edge, 64 source
+//   indices per coalesced load with the next block prefetched, U row loads in flight, masked
+//   columns -- with the reducer in place of the fma: idle edge slots and the < STEP remainder hold
+//   the identity (-inf), the LPE < 64 butterfly folds with the reducer, split rows write their
+//   partial maxima and k_reduce_combine folds them (any order gives the same value).
+//   MIN runs as -max(-x): sbit (0 or the sign bit, wave-uniform) flips every value on its way in
+//   and the result on its way out, which is exact, so one instantiation serves both.
+//   red_max propagates NaN (an explicit compare-and-select plus the unordered test; fmaxf would
+//   drop it, and with it the guard-band arena's poison) and picks one of its operands' bits.
+//   A row without edges gets 0, decided by its degree.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float red_max(float a, float t) { return (t > a || t != t) ? t : a; }
+__device__ __forceinline__ float red_flip(float v, uint32_t sbit) { return __uint_as_float(__float_as_uint(v) ^ sbit); }
+
+template <int LPE, int VW, int NV, int XMODE, typename TX = float>
+__global__ void __launch_bounds__(kBlock)
+k_reduce(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows, PlanView plan,
+         int use_plan, int x_is_row, const TX* __restrict__ x, int64_t ldx, int F, uint32_t sbit,
+         float* __restrict__ y, int64_t ldy, float* __restrict__ partial) {
+  constexpr int EPI = kWave / LPE;  // edges per wave instruction
+  constexpr int XB = NV * VW * static_cast<int>(sizeof(TX));
+  constexpr int UR = (64 / XB) < 2 ? 2 : ((64 / XB) > 8 ? 8 : 64 / XB);  // ~64 B of rows in flight per lane
+  constexpr int STEP = UR * EPI;
+  const float ident = -__builtin_inff();
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t item = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  const int64_t n_items = use_plan ? plan.hdr[0] : n_rows;
+  if (item >= n_items) return;
+
+  int64_t row, eb, ee;
+  bool split = false;
+  if (use_plan) {
+    const int32_t ir = plan.item_row[item];
+    row = ir & 0x7fffffff;
+    eb = plan.item_beg[item];
+    ee = plan.item_end[item];
+    split = ir < 0;
+  } else {
+    row = item;
+    eb = indptr[row];
+    ee = indptr[row + 1];
+  }
+  const bool empty = eb >= ee;  // a whole row without edges (an item of a split row is never empty)
+  const int sub = (LPE == kWave) ? 0 : lane / LPE;
+  const int cl = (LPE == kWave) ? lane : lane % LPE;
+
+  for (int c0 = 0; c0 < F; c0 += LPE * VW * NV) {
+    int col[NV], lo[NV];
+    bool cval[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int c = c0 + (v * LPE + cl) * VW;
+      cval[v] = c < F;
+      int cc = cval[v] ? c : 0;
+      lo[v] = 0;
+      if constexpr (VW == 8) {  // 16-B bf16 pieces, F % 4 == 0: the last lane's piece starts 4 early
+        if (cval[v] && cc + VW > F) { lo[v] = cc + VW - F; cc -= lo[v]; }
+      }
+      col[v] = cc;
+    }
+    float acc[NV][VW];
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int k = 0; k < VW; ++k) acc[v][k] = ident;
+
+    const bool use_idx = (XMODE == XM_IDX) && !x_is_row;
+    int idxv = 0;
+    if (use_idx && eb < ee) idxv = indices[min(eb + lane, ee - 1)];
+    for (int64_t e0 = eb; e0 < ee; e0 += kWave) {
+      const int n = static_cast<int>(min<int64_t>(kWave, ee - e0));
+      int idxn = 0;
+      if (use_idx) idxn = indices[min(e0 + kWave + lane, ee - 1)];  // clamped: the load is unconditional
+      for (int s = 0; s < n; s += STEP) {
+        Vec<VW> xv[UR][NV];
+        bool valid[UR];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+          const int j = s + u * EPI + sub;
+          valid[u] = j < n;
+          const int jj = j < n ? j : n - 1;
+          int64_t xr;
+          if (XMODE == XM_EDGE) {
+            xr = e0 + jj;
+          } else if (x_is_row) {
+            xr = row;
+          } else if (LPE == kWave) {
+            xr = __builtin_amdgcn_readlane(idxv, jj);
+          } else {
+            xr = __shfl(idxv, jj);
+          }
+          const TX* xp = x + xr * ldx;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) load_row(xv[u][v], xp + col[v]);
+        }
+#pragma unroll
+        for (int u = 0; u < UR; ++u)
+#pragma unroll
+          for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int k = 0; k < VW; ++k)
+              acc[v][k] = red_max(acc[v][k], valid[u] ? red_flip(xv[u][v].v[k], sbit) : ident);
+      }
+      idxv = idxn;
+    }
+    if (LPE < kWave) {  // fold the EPI edge slots with the reducer
+#pragma unroll
+      for (int off = LPE; off < kWave; off <<= 1)
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+          for (int k = 0; k < VW; ++k) acc[v][k] = red_max(acc[v][k], __shfl_xor(acc[v][k], off));
+    }
+    if (sub == 0) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        if (!cval[v]) continue;
+        Vec<VW> o;
+        // a split item's partial stays in the max domain (k_reduce_combine flips the folded value)
+#pragma unroll
+        for (int k = 0; k < VW; ++k) o.v[k] = split ? acc[v][k] : (empty ? 0.f : red_flip(acc[v][k], sbit));
+        float* p = split ? partial + item * static_cast<int64_t>(F) + col[v] : y + row * ldy + col[v];
+        if constexpr (VW == 8) {  // a piece whose first lo values belong to the lane before: its upper half only
+          if (lo[v]) { *reinterpret_cast<float4*>(p + 4) = make_float4(o.v[4], o.v[5], o.v[6], o.v[7]); continue; }
+        }
+        o.store(p);
+      }
+    }
+  }
+}
+
+// fold the chunk partials of split rows (max domain) and flip the result back
+__global__ void __launch_bounds__(kBlock)
+k_reduce_combine(PlanView plan, int F, uint32_t sbit, float* __restrict__ y, int64_t ldy,
+                 const float* __restrict__ partial) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t s = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  if (s >= plan.hdr[1]) return;
+  const int64_t row = plan.split_row[s];
+  const int64_t first = plan.split_first[s];
+  const int cnt = plan.split_cnt[s];
+  for (int c = lane; c < F; c += kWave) {
+    float a = -__builtin_inff();
+    for (int j = 0; j < cnt; ++j) a = red_max(a, partial[(first + j) * F + c]);
+    y[row * ldy + c] = red_flip(a, sbit);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Lean aggregate for rows that exactly fill a wavefront (F = 64 * VW): one edge
 // per wave instruction, wave-uniform row base.  Per unrolled step of U edges:
 //   * U row loads issued back to back, no per-edge validity select (full steps
@@ -4403,6 +4553,132 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
   }
   return GTA_OK;
 }
+
+// host-side dispatch of k_reduce (gta_reduce MAX / MIN): aggregate_impl's choice of LPE / VW / NV
+template <int LPE, int VW, int NV, int XM, typename TX>
+void launch_red(const AggArgs& a, uint32_t sbit, int64_t n_items_bound, hipStream_t s) {
+  const int64_t blocks = (n_items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
+  k_reduce<LPE, VW, NV, XM, TX><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(
+      a.indptr, a.indices, a.n_rows, a.plan, a.use_plan, a.x_is_row, static_cast<const TX*>(a.x), a.ldx, a.F, sbit,
+      a.y, a.ldy, a.partial);
+}
+
+template <int LPE, int VW, int NV>
+bool dispatch_red_x(int xm, bool bf, const AggArgs& a, uint32_t sbit, int64_t nb, hipStream_t s) {
+  if (bf) {  // bf16 rows are gathered by index only
+    if (xm != XM_IDX) return false;
+    launch_red<LPE, VW, NV, XM_IDX, uint16_t>(a, sbit, nb, s);
+  } else if (xm == XM_EDGE) {
+    launch_red<LPE, VW, NV, XM_EDGE, float>(a, sbit, nb, s);
+  } else {
+    launch_red<LPE, VW, NV, XM_IDX, float>(a, sbit, nb, s);
+  }
+  return true;
+}
+
+template <int VW>
+bool dispatch_red_lpe(int lpe, int nv, int xm, bool bf, const AggArgs& a, uint32_t sbit, int64_t nb, hipStream_t s) {
+  switch (lpe) {
+    case 64:
+      if (nv == 1) return dispatch_red_x<64, VW, 1>(xm, bf, a, sbit, nb, s);
+      if (nv == 2) return dispatch_red_x<64, VW, 2>(xm, bf, a, sbit, nb, s);
+      return dispatch_red_x<64, VW, 4>(xm, bf, a, sbit, nb, s);
+    case 32: return dispatch_red_x<32, VW, 1>(xm, bf, a, sbit, nb, s);
+    case 16: return dispatch_red_x<16, VW, 1>(xm, bf, a, sbit, nb, s);
+    case 8: return dispatch_red_x<8, VW, 1>(xm, bf, a, sbit, nb, s);
+    default: return dispatch_red_x<4, VW, 1>(xm, bf, a, sbit, nb, s);
+  }
+}
+
+bool dispatch_red_vw8(int lpe, const AggArgs& a, uint32_t sbit, int64_t nb, hipStream_t s) {
+  switch (lpe) {
+    case 64: launch_red<64, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
+    case 32: launch_red<32, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
+    case 16: launch_red<16, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
+    case 8: launch_red<8, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
+    case 4: launch_red<4, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
+  }
+  return false;
+}
+
+int reduce_impl(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
+                const void* x, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy, const void* plan,
+                int64_t plan_chunk, void* workspace, void* stream) {
+  const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
+  if (n_rows < 0 || nnz < 0 || F <= 0) return fail(GTA_ERR_ARG, "reduce: bad sizes");
+  if (x_mode != GTA_IDX_EDGE && x_mode != GTA_IDX_SRC && x_mode != GTA_IDX_DST)
+    return fail(GTA_ERR_ARG, "reduce: bad x_mode");
+  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, "reduce: x_dtype must be F32 or BF16");
+  const bool bf = x_dtype == GTA_BF16;
+  const int xe = bf ? 2 : 4;  // bytes per x element
+  if (bf && x_mode == GTA_IDX_EDGE)
+    return fail(GTA_ERR_UNSUPPORTED, "reduce: bf16 rows are gathered by index (SRC / DST)");
+  if (F > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, "reduce: F too large");
+  if (n_rows == 0) return GTA_OK;
+  // with no edges, x and indices are never read (may be NULL); every row gets 0
+  if (!indptr || !y || (nnz > 0 && !x) || ldy < F || (nnz > 0 && ldx < F)) return fail(GTA_ERR_ARG, "reduce: bad arguments");
+  if (x_mode == GTA_IDX_SRC && !indices && nnz > 0) return fail(GTA_ERR_ARG, "reduce: x_mode SRC needs indices");
+  if (nnz == 0) { x = y; ldx = ldy; }  // any valid address: no row has an edge to read
+  const int xm = (x_mode == GTA_IDX_EDGE) ? XM_EDGE : XM_IDX;
+  auto ok_vw = [&](int vw) {
+    return !(F % vw || ldx % vw || ldy % vw || !aligned(x, xe * vw) || !aligned(y, 4 * vw));
+  };
+  int vw = ok_vw(4) ? 4 : (ok_vw(2) ? 2 : 1);
+  if (tuning().force_vw && tuning().force_vw <= vw && ok_vw(tuning().force_vw)) vw = tuning().force_vw;
+  // one edge per wave instruction whenever the row fills 64 lanes at >= 8 B per lane (as the aggregate)
+  if (!bf && vw == 4 && F < 4 * kWave && F >= 2 * kWave && ok_vw(2)) vw = 2;
+  const int64_t lanes = (F + vw - 1) / vw;
+  int lpe, nv = 1;
+  if (lanes >= kWave) {
+    lpe = kWave;
+    nv = lanes >= 4 * kWave ? 4 : (lanes > kWave ? 2 : 1);
+  } else {
+    lpe = 4;
+    while (lpe < lanes) lpe <<= 1;
+  }
+  // bf16 rows in 16-B pieces (8 elements per lane, the last lane's piece clamped inside the row)
+  bool vw8 = false;
+  if (bf && nnz > 0 && tuning().agg_bf16_vw8 && !tuning().force_vw && F % 4 == 0 && F >= 8 && F <= 512 && ldx % 4 == 0 &&
+      aligned(x, 8) && ldy % 4 == 0 && aligned(y, 16)) {
+    const int64_t ln = (F + 7) / 8;
+    vw8 = true;
+    vw = 8;
+    nv = 1;
+    lpe = 4;
+    while (lpe < ln) lpe <<= 1;
+  }
+  AggArgs a{};
+  a.indptr = indptr; a.indices = indices; a.n_rows = n_rows;
+  a.use_plan = plan != nullptr; a.chunk = plan_chunk; a.x_is_row = (x_mode == GTA_IDX_DST);
+  a.x = x; a.ldx = ldx; a.F = static_cast<int>(F); a.y = y; a.ldy = ldy;
+  a.partial = static_cast<float*>(workspace);
+  int64_t bound = n_rows;
+  if (plan) {
+    if (plan_chunk <= 0 || !workspace) return fail(GTA_ERR_ARG, "reduce: plan needs chunk and workspace");
+    bound = max_items_for(n_rows, nnz, plan_chunk);
+    a.plan = plan_view(const_cast<void*>(plan), n_rows, bound);
+  }
+  const uint32_t sbit = red == GTA_RED_MIN ? 0x80000000u : 0u;
+  hipStream_t s = S(stream);
+  bool ok = false;
+  if (vw8) ok = dispatch_red_vw8(lpe, a, sbit, bound, s);
+  else switch (vw) {
+    case 4: ok = dispatch_red_lpe<4>(lpe, nv, xm, bf, a, sbit, bound, s); break;
+    case 2: ok = dispatch_red_lpe<2>(lpe, nv, xm, bf, a, sbit, bound, s); break;
+    default: ok = dispatch_red_lpe<1>(lpe, nv, xm, bf, a, sbit, bound, s); break;
+  }
+  if (!ok) return fail(GTA_ERR_UNSUPPORTED, "reduce: no kernel variant");
+  GTA_LAUNCHED("k_reduce");
+  if (plan) {
+    const int64_t sb = (nnz + plan_chunk - 1) / plan_chunk;  // >= number of split rows
+    if (sb > 0) {
+      const int64_t blocks = (sb + kWavesPerBlock - 1) / kWavesPerBlock;
+      k_reduce_combine<<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(a.plan, a.F, sbit, y, ldy, a.partial);
+      GTA_LAUNCHED("k_reduce_combine");
+    }
+  }
+  return GTA_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -4412,6 +4688,20 @@ int gta_aggregate(const int64_t* indptr, const int32_t* indices, int64_t n_rows,
                   int64_t plan_chunk, void* workspace, void* stream) {
   return aggregate_impl(indptr, indices, n_rows, nnz, x_mode, x, ldx, F, x_dtype, w, ldw, heads, row_scale, y, ldy,
                         accumulate, plan, plan_chunk, workspace, stream, nullptr, 0, nullptr);
+}
+
+int gta_reduce(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
+               const void* x, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy, const void* plan,
+               int64_t plan_chunk, void* workspace, void* stream) {
+  if (red == GTA_RED_ADD) {  // the sum is gta_aggregate's: no weights, no row scale, no accumulate
+    const int rc = aggregate_impl(indptr, indices, n_rows, nnz, x_mode, x, ldx, F, x_dtype, nullptr, 0, 0, nullptr, y,
+                                  ldy, 0, plan, plan_chunk, workspace, stream, nullptr, 0, nullptr);
+    return rc < 0 ? fail(rc, "reduce (ADD): " + g_err) : rc;
+  }
+  if (red != GTA_RED_MAX && red != GTA_RED_MIN)
+    return fail(GTA_ERR_ARG, "reduce: red must be GTA_RED_ADD, GTA_RED_MAX or GTA_RED_MIN");
+  return reduce_impl(red, indptr, indices, n_rows, nnz, x_mode, x, ldx, F, x_dtype, y, ldy, plan, plan_chunk,
+                     workspace, stream);
 }
 
 int gta_aggregate_expr(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int shape,

@@ -17,6 +17,8 @@ reads the same two YAML files, and runs the stream on real device tensors:
         hardware_info.yaml Inst_fused) becomes one aggregate kernel (MUL) or
         an edge GEMM + gather (MM);
       - scatters with a STORE_E are materialised with gta_scatter;
+      - a gather reduces with its COMP_TYPE: ADD on the aggregate kernels and every fusion above,
+        MAX / MIN on gta_reduce, MEAN on the aggregate with row_scale = 1/deg (_eval_reduce);
   * numerics the YAML leaves open come from semantics.py.
 Returns ExecResult(values per op, outputs of sink ops, elapsed_s, alg_bytes).
 """
@@ -140,6 +142,21 @@ class ExecResult:
 
 def _forced(v):
     return v.force() if isinstance(v, Lazy) else v
+
+
+REDUCERS = ("MAX", "MIN", "MEAN")  # gather COMP_TYPEs beside the sum (Executor._eval_reduce)
+
+
+def _mean_scale(g):
+    """float32 [n_rows]: 1 / deg of every row of graph g (a CSR, or a CSC view: the out-degree), rows
+    without edges 1 (their sum is 0).  Built once per graph or view and kept beside its plans; no
+    host sync.  A capture's first use is not kept: its tensor belongs to the graph's private pool."""
+    s = g._plans.get("mean_scale")
+    if s is None:
+        s = 1.0 / g.degrees().to(torch.float32).clamp_min(1.0)
+        if not (s.is_cuda and torch.cuda.is_current_stream_capturing()):
+            g._plans["mean_scale"] = s
+    return s
 
 
 EDGE_EXPR = True  # Executor.edge_expr's default (gta_aggregate_expr for applyedge trees); False: unfused (A/B)
@@ -334,7 +351,7 @@ class Executor:
             if v is None or ops_[v].type != "applyedge" or ops_[v].comp != "SF":
                 continue
             gs = [c for c in cons[v] if ops_[c].type == "gather" and ops_[c].order == "R"]
-            if len(gs) != 1:
+            if len(gs) != 1 or ops_[gs[0]].comp != "ADD":  # the chain's gather is the softmax SUM
                 continue
             G = gs[0]
             pat = {"A": A.idx, "V": v, "G": G, "D": None}
@@ -354,8 +371,8 @@ class Executor:
         reading a scatter C directly or through a (weight) MUL (GraphSAGE / GCN layer 1)."""
         found = {}
         for G in self.g.ops:
-            if G.type != "gather" or G.order != "R" or len(self.consumers[G.idx]) != 1:
-                continue
+            if G.type != "gather" or G.order != "R" or G.comp != "ADD" or len(self.consumers[G.idx]) != 1:
+                continue  # (sum_e w x) W == sum_e w (x W) holds for the sum only
             M = self.g.ops[self.consumers[G.idx][0]]
             if M.type != "applynode" or M.comp != "MM" or len(self.g.inputs[M.idx]) != 1:
                 continue
@@ -561,7 +578,7 @@ class Executor:
                 continue
             gs = 0 if kinds[0] == "gather" else 1
             G, T = self.g.ops[ins[gs].op], self.g.ops[ins[1 - gs].op]
-            if G.order != "R" or self.consumers[G.idx] != [A.idx] or self.consumers[T.idx] != [A.idx]:
+            if G.order != "R" or G.comp != "ADD" or self.consumers[G.idx] != [A.idx] or self.consumers[T.idx] != [A.idx]:
                 continue
             if T.comp not in ("ADD", "MUL") or len(self.g.inputs[T.idx]) != 2:
                 continue
@@ -815,7 +832,8 @@ class Executor:
             S = other[0]
             if ops_[S].type != "scatter" or ops_[S].order != "C":
                 continue
-            if len(cons[M]) != 1 or ops_[cons[M][0]].type != "gather" or ops_[cons[M][0]].order != "R":
+            if len(cons[M]) != 1 or ops_[cons[M][0]].type != "gather" or ops_[cons[M][0]].order != "R" \
+                    or ops_[cons[M][0]].comp != "ADD":
                 continue
             found[M] = (pat, cons[M][0], S)
         return found
@@ -954,6 +972,8 @@ class Executor:
     def _eval_gather(self, op, acc=None, self_term=None, out_dtype=torch.float32):
         """self_term (x, s): y = x * s + the aggregate, or None if this gather's form cannot take it;
         out_dtype (self_term only): y's storage dtype."""
+        if op.comp in REDUCERS:  # COMP_TYPE MAX / MIN / MEAN: no accumulate, no self term, none of the sum's fusions
+            return None if (acc is not None or self_term is not None) else self._eval_reduce(op)
         if op.order == "C":
             if acc is not None or self_term is not None:
                 return None
@@ -1022,6 +1042,47 @@ class Executor:
 
     def _plan(self):
         return self.plan_chunk if self.plan_chunk else None
+
+    def _eval_reduce(self, op):
+        """The ISA gather whose COMP_TYPE is MAX, MIN or MEAN (include/gta.h gta_reduce; the sum's
+        COMP_TYPE is ADD), both DIRECTIONs.  A virtual scatter is reduced by index straight from the
+        node table (fp32 or bf16; no [E, F] tensor); everything else -- an edge tensor, or a fused
+        applyedge MUL / MM producer, which is first formed as the unfused op forms it -- in EDGE
+        mode.  MAX / MIN run gta_reduce; MEAN is the plain ADD aggregate with row_scale = 1 / deg
+        (empty rows 0).  ORDER C runs the same kernels over the graph's CSC views, the degree then
+        the out-degree from colptr.  None of the rewrites that rely on the gather being a sum applies
+        (mm_first, two_hop, gather_acc, the weighted aggregate, the attention chains, edge_expr)."""
+        d = self.dist
+        if d is not None and d.s.world > 1 and (not d.local_rows or op.order == "C"):
+            raise NotImplementedError(
+                f"op {op.idx}: gather {op.comp} on a shard that holds only part of each output node's edges "
+                "(partial maxima / means cannot be summed across ranks); row-local shards of an ORDER R gather work")
+        v = self._source(op, 0)
+        if isinstance(v, Deferred):
+            v = self._materialize_deferred(v)
+        E, F4 = self.graph.nnz, 4
+        if op.order == "C":
+            c = ops.csc(self.graph)
+            n_out = self.graph.n_cols
+            if isinstance(v, Scat):
+                t, g, mode = v.t, c.view("dst" if v.mode == "dst" else "src"), "src"
+            else:
+                t, g, mode = self._to_edge_tensor(v), c.view("edge"), "src"
+            nbytes = E * (4 + t.shape[1] * t.element_size()) + n_out * (8 + t.shape[1] * F4)
+        else:
+            n_out = self.graph.n_rows
+            if isinstance(v, Scat):
+                t, g, mode = v.t, self.graph, v.mode
+                nbytes = E * (4 + t.shape[1] * F4) + n_out * (8 + t.shape[1] * F4)
+            else:
+                t, g, mode = self._to_edge_tensor(v), self.graph, "edge"
+                nbytes = E * t.shape[1] * F4 + n_out * (8 + t.shape[1] * F4)
+        if op.comp == "MEAN":
+            y = ops.aggregate(g, t, mode, None, row_scale=_mean_scale(g), plan=self._plan())
+        else:
+            y = ops.reduce(g, t, op.comp, mode, plan=self._plan())
+        self._count(nbytes)
+        return NodeT(y)
 
     def _eval_gather_c(self, op):
         """ISA gather with DIRECTION src (ORDER C, template/ISA_defination.yaml:46-48): y[j] = sum of

@@ -146,16 +146,32 @@ def _size(sym, env):
     return v * 4
 
 
-def gen_ops(network, layer, node_num, edge_num, feature, reorder=False, heads=16):
-    """Op-graph records for one layer (what gen_yaml writes, genGraphOP.py:27-154)."""
+AGGREGATORS = ("ADD", "MAX", "MIN", "MEAN")  # COMP_TYPE values of a message gather (ADD: genGraphOP's)
+
+
+def gen_ops(network, layer, node_num, edge_num, feature, reorder=False, heads=16, aggregator="ADD"):
+    """Op-graph records for one layer (what gen_yaml writes, genGraphOP.py:27-154).
+
+    aggregator: the reduce function of the network's message gathers -- the gather op's COMP_TYPE
+    (the ISA gather carries it as a field: COMPUTE mul: add, template/ISA_defination.yaml:58-61).
+    "ADD" is genGraphOP's output unchanged; "MAX" / "MIN" / "MEAN" rewrite the COMP_TYPE of every
+    gather of the layer (both hops of SGC) and nothing else: GraphSAGE-pool's max, PNA's max / min
+    / mean, GCN- and SAGE-mean.  GAT's gathers are its softmax sums, not a message reducer: any
+    other aggregator than ADD raises ValueError."""
     key = (network, bool(reorder))
     rows = TABLE.get(key, TABLE.get(network))
     if rows is None:
         raise ValueError(f"no such network {network}")
+    if aggregator not in AGGREGATORS:
+        raise ValueError(f"aggregator must be one of {AGGREGATORS} (got {aggregator!r})")
+    if aggregator != "ADD" and network == "GAT":
+        raise ValueError("GAT's gathers are the sums of its edge softmax: it takes no aggregator but ADD")
     env = {"fin": [0, feature, 128, 64, 16][layer], "fout": [0, 128, 64, 16][layer], "fh": heads}
     count = {_N: node_num, _E: edge_num}
     out = []
     for no, comp, kind, order, fnum, ins, g, nong, w, isz, outs, onum, osz in rows:
+        if kind == "gather" and comp == "ADD":
+            comp = aggregator
         out.append({
             "OP_NO": no, "COMP_TYPE": comp, "TYPE": kind, "ORDER": order,
             "INPUT": {"input_g_list": list(ins), "input_g_num": g, "input_nong_num": nong, "input_nong_list": [],
@@ -167,10 +183,11 @@ def gen_ops(network, layer, node_num, edge_num, feature, reorder=False, heads=16
     return out
 
 
-def gen_yaml(path, node_num, edge_num, size_per_feature, network, layer, isReorder, heads=16):
-    """Same call and output as genGraphOP.gen_yaml (+ optional attention width `heads`)."""
+def gen_yaml(path, node_num, edge_num, size_per_feature, network, layer, isReorder, heads=16, aggregator="ADD"):
+    """Same call and output as genGraphOP.gen_yaml (+ optional attention width `heads` and message
+    `aggregator`, see gen_ops)."""
     import os
-    data = gen_ops(network, layer, node_num, edge_num, size_per_feature, isReorder, heads)
+    data = gen_ops(network, layer, node_num, edge_num, size_per_feature, isReorder, heads, aggregator)
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)

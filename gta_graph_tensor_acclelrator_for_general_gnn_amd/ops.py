@@ -5,6 +5,8 @@ One function per ISA op / fused pattern of the GTA stream:
   gather_add   ISA `gather` R/C (template/ISA_defination.yaml:46-61)      -> gta_gather_add (+ gta_csc_build for C)
   aggregate    fused applyedge MUL -> gather ADD (+ removed scatter FETCH)
                (hardware_info.yaml Inst_fused :35-38, code/interpreter.py:575-636, 764-802) -> gta_aggregate
+  reduce       ISA `gather` with COMP_TYPE MAX / MIN: rows without edges 0, NaN propagates, every
+               output bitwise one of its inputs (+0 / -0 apart)             -> gta_reduce
   apply_edge   applyedge ADD/MUL/SF (genGraphOP.py:36, 55-60)              -> gta_apply_edge
   aggregate_expr  a tree of applyedge ops -> gather ADD, fused (DGN, PNA)   -> gta_aggregate_expr
   apply_node   applynode ADD/MUL/SF (genGraphOP.py:62, 94-95, 103-108)     -> gta_apply_node
@@ -229,6 +231,58 @@ def aggregate(graph, x, x_mode="src", w=None, row_scale=None, out=None, accumula
     check(_L().gta_aggregate(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz, _MODES[x_mode],
                              _ptr(x), ldx, F, x_dt, _ptr(w), ldw, heads, _ptr(row_scale), _ptr(out), ldy,
                              int(bool(accumulate)), _ptr(pbuf), chunk, _ptr(ws), _stream(x.device)), "aggregate")
+    return out
+
+
+_REDS = {"ADD": _lib.RED_ADD, "MAX": _lib.RED_MAX, "MIN": _lib.RED_MIN}
+
+
+def reduce(graph, x, red="MAX", x_mode="src", out=None, plan=None):
+    """y[i] = red over the edges e of row i of x[idx(e)] (gta_reduce, ABI 15): the ISA gather with
+    COMP_TYPE MAX / MIN ("ADD": the unweighted aggregate).
+
+    Rows without edges get 0 (decided by the degree: an all -inf row gives -inf under MAX); NaN
+    propagates; +0 / -0 apart, every output element is bitwise one of its inputs, so the result does
+    not depend on plan or kernel form.  x float32, or bfloat16 for "src" / "dst" (widened exactly);
+    y float32.  No weights, row_scale or accumulate (MEAN is aggregate(..., row_scale=1/deg)).
+    x_mode, plan: as aggregate (plan an AggregatePlan or an int chunk: the cached plan, dropped when
+    no row is split).  graph may be a CSC.view(...): the reduce to the SOURCE nodes (direction C)."""
+    _need_gpu(x, out, graph.indptr)
+    if red not in _REDS:
+        raise ValueError(f"reduce: red must be one of {sorted(_REDS)} (got {red!r})")
+    if x_mode not in _MODES:
+        raise ValueError(f"reduce: x_mode must be one of {sorted(_MODES)} (got {x_mode!r})")
+    F = x.shape[1]
+    if x.dtype == torch.bfloat16 and x_mode == "edge":
+        raise TypeError("reduce: bfloat16 rows are gathered by index (src / dst)")
+    ldx = _rows(x, "x", torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32)
+    x_dt = _lib.GTA_BF16 if x.dtype == torch.bfloat16 else _lib.GTA_F32
+    if x_mode == "edge" and x.shape[0] < graph.nnz:
+        raise ValueError("edge-mode x must have E rows")
+    if x_mode == "src" and x.shape[0] < graph.n_cols:
+        raise ValueError("src-mode x must have n_cols rows")
+    if x_mode == "dst" and x.shape[0] < graph.n_rows:
+        raise ValueError("dst-mode x must have n_rows rows")
+    if out is None:
+        out = torch.empty(graph.n_rows, F, dtype=torch.float32, device=x.device)
+    ldy = _rows(out, "out")
+    if out.shape[0] < graph.n_rows or out.shape[1] != F:
+        raise ValueError("out must be [N, F]")
+    if graph.n_rows == 0:
+        return out
+    if isinstance(plan, int):
+        plan = graph.plan(plan)
+        if plan.splits == 0:  # no row is split: the per-row form (same values, no combine launch)
+            plan = None
+    pbuf = ws = None
+    chunk = 0
+    if plan is not None:
+        if plan.graph is not graph:
+            raise ValueError("plan built for another graph")
+        pbuf, ws, chunk = plan.buf, plan.workspace(F), plan.chunk
+    check(_L().gta_reduce(_REDS[red], _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz, _MODES[x_mode],
+                          _ptr(x), ldx, F, x_dt, _ptr(out), ldy, _ptr(pbuf), chunk, _ptr(ws), _stream(x.device)),
+          "reduce")
     return out
 
 

@@ -16,12 +16,15 @@ class Layer:
     """One compiled GNN layer bound to a graph: op graph, chosen partition, stream."""
 
     def __init__(self, network, layer, graph, feature, reorder=False, heads=16, candidate=0, tile_start=None,
-                 op_array=None, tile_size_list=None, metadata=None, pingpang=True, sinput=False):
+                 op_array=None, tile_size_list=None, metadata=None, pingpang=True, sinput=False, aggregator="ADD"):
         """pingpang / sinput: compile()'s isPingpang / isSinput (code/compiler.py:475-510) for the
-        fusion search; the reference's start.py passes its command-line flags through."""
+        fusion search; the reference's start.py passes its command-line flags through.
+        aggregator: the message gathers' reduce function, "ADD" / "MAX" / "MIN" / "MEAN"
+        (frontend.gen_ops; the gathers' COMP_TYPE, executed by gta_reduce / the scaled aggregate)."""
         self.network, self.layer, self.reorder = network, layer, reorder
+        self.aggregator = aggregator
         self.graph = graph
-        self.records = frontend.gen_ops(network, layer, graph.n_rows, graph.nnz, feature, reorder, heads)
+        self.records = frontend.gen_ops(network, layer, graph.n_rows, graph.nnz, feature, reorder, heads, aggregator)
         self.sem = Semantics.for_network(network, reorder)
         self.opgraph = ir.OpGraph(self.records, self.sem.inputs)
         if op_array is None:

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GTA_ABI_VERSION 14 /* 2: blocked plans of bounded items (nnz, item_edges); 3: per-thread tuning
+#define GTA_ABI_VERSION 15 /* 2: blocked plans of bounded items (nnz, item_edges); 3: per-thread tuning
                               hooks; 4: knob sets attached to streams (gta_tuning_*); 5: every UPDATE
                               on hand-written kernels (no vendor library), gta_update_mm_t_splits,
                               the blocked workspace is the slab rows alone and required, bf16
@@ -49,7 +49,7 @@ extern "C" {
                               gta_aggregate_self, bf16 x of gta_update_mlp; 11: gta_gather_add takes the ISA
                               DIRECTION (dir R / C) and the CSC view of gta_csc_build; 12:
                               gta_build_id, gta_synth_alpha and gta_row_ids (scan-free setup); 13: gta_apply_edge_flat;
-                              14: gta_aggregate_expr */
+                              14: gta_aggregate_expr; 15: gta_reduce (gather MAX / MIN) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -164,6 +164,33 @@ int gta_aggregate_expr(const int64_t* indptr, const int32_t* indices, int64_t n_
                        const float* const* operands, const int* modes, const int64_t* lds, const int* bins,
                        const int* sfs, int swap, int64_t F, float* y, int64_t ldy, const void* plan,
                        int64_t plan_chunk, void* workspace, void* stream);
+
+/* ---- K2' REDUCE (gather with COMP_TYPE MAX / MIN; ABI 15) ------------------
+ * The ISA's gather carries its reduce function as a field (COMPUTE: formula i,i->i, mul: add,
+ * template/ISA_defination.yaml:58-61) and every op record a COMP_TYPE; gta_aggregate executes
+ * the sum, this entry point the other reducers of the GNN aggregators (GraphSAGE-pool's max,
+ * PNA's max / min):
+ *   red GTA_RED_MAX / GTA_RED_MIN:  y[i, c] = max / min over the edges e of row i of x[idx(e), c]
+ *   red GTA_RED_ADD:                gta_aggregate with w NULL, no row_scale, no accumulate
+ * idx follows x_mode (GTA_IDX_SRC / GTA_IDX_DST / GTA_IDX_EDGE) exactly as in gta_aggregate.
+ *  - A row with no edges gets 0.0f (the ADD gather's value for it), decided from the row's degree:
+ *    a row whose every value is -inf yields -inf under MAX.
+ *  - NaN propagates: if any edge value of (row, column) is NaN the result is NaN (an out-of-range
+ *    read of a NaN-poisoned guard band therefore shows in y instead of being swallowed).
+ *  - +0 and -0 compare equal and which one is returned is unspecified; apart from that every output
+ *    element is bitwise one of its inputs, so y does not depend on plan, chunk, vector width or
+ *    kernel form.
+ *  - x_dtype GTA_F32, or GTA_BF16 for x_mode SRC / DST (rows widened exactly); y is always fp32.
+ *    No weights, no row_scale, no accumulate.  MEAN is gta_aggregate with row_scale = 1/deg.
+ * plan / workspace: those of gta_aggregate_plan_build / gta_aggregate_workspace_bytes (the same
+ * item list, the same [items, F] fp32 partials; a split row's partial maxima are folded by a
+ * second small kernel, in any order the same value).
+ * Errors: bad red / x_mode / x_dtype GTA_ERR_ARG; bf16 with x_mode EDGE GTA_ERR_UNSUPPORTED.
+ * nnz == 0: y all zero, x and indices never read (may be NULL). */
+enum { GTA_RED_ADD = 0, GTA_RED_MAX = 1, GTA_RED_MIN = 2 };
+int gta_reduce(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
+               int x_mode, const void* x, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy,
+               const void* plan, int64_t plan_chunk, void* workspace, void* stream);
 
 /* ABI 7: the aggregate with a self term, y[i, :] = self_scale[0] * x_self[i, :] + row_scale[i] *
  * sum_{e in row i} w(e) x[idx(e), :] (no accumulate).  x_self has x's dtype and F columns (ld_self
