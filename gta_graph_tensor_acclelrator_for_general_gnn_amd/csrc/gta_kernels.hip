@@ -357,6 +357,56 @@ __device__ __forceinline__ void expr_eval(int code, float (&L)[4][M], float* t) 
 // of a narrow row); the same product and sum per element, so bitwise equal to WM_HEAD at H = 1
 enum { WM_NONE = 0, WM_HEAD = 1, WM_FULL = 2, WM_EDGE1 = 3 };
 
+// Shared parts of the per-row gather kernels (k_aggregate, k_reduce, k_agg_lean, k_agg_expr).
+// A wave's work item: a whole row, or with a plan a <= chunk slice [eb, ee) of one; split: the
+// row has several items, each writing a partial that a combine kernel folds.
+struct WorkItem {
+  int64_t row, eb, ee;
+  bool split;
+};
+
+__device__ __forceinline__ WorkItem work_item(const int64_t* __restrict__ indptr, const PlanView& plan, int use_plan,
+                                              int64_t item) {
+  if (use_plan) {
+    const int32_t ir = plan.item_row[item];
+    return {ir & 0x7fffffff, plan.item_beg[item], plan.item_end[item], ir < 0};
+  }
+  return {item, indptr[item], indptr[item + 1], false};
+}
+
+// one piece of the generic form: VW elements of the row from column c on (valid: inside the row)
+struct Piece {
+  int col, lo;
+  bool valid;
+};
+
+template <int VW>
+__device__ __forceinline__ Piece piece_at(int c, int F) {
+  Piece p{c < F ? c : 0, 0, c < F};
+  if constexpr (VW == 8) {  // 16-B bf16 pieces, F % 4 == 0: the last lane's piece starts 4 early
+    if (p.valid && p.col + VW > F) { p.lo = p.col + VW - F; p.col -= p.lo; }  // (its first lo values unused)
+  }
+  return p;
+}
+
+// the row that edge e0 + jj of the item gathers; idxv: this block's 64 source indices, one per lane
+template <int LPE, int XMODE>
+__device__ __forceinline__ int64_t gather_row(int64_t e0, int jj, int64_t row, int x_is_row, int idxv) {
+  if (XMODE == XM_EDGE) return e0 + jj;
+  if (x_is_row) return row;
+  if (LPE == kWave) return __builtin_amdgcn_readlane(idxv, jj);
+  return __shfl(idxv, jj);
+}
+
+// a piece whose first lo values belong to the lane before: store its upper half only
+template <int VW>
+__device__ __forceinline__ void store_piece(const Vec<VW>& o, float* p, int lo) {
+  if constexpr (VW == 8) {
+    if (lo) { *reinterpret_cast<float4*>(p + 4) = make_float4(o.v[4], o.v[5], o.v[6], o.v[7]); return; }
+  }
+  o.store(p);
+}
+
 // TX: the gathered rows' element type (float, or bf16 as uint16_t: widened exactly, fp32 sums)
 template <int LPE, int VW, int NV, int XMODE, int WMODE, typename TX = float, int URX = 0>
 __global__ void __launch_bounds__(kBlock)
@@ -385,19 +435,7 @@ k_aggregate(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indi
   const int64_t n_items = use_plan ? plan.hdr[0] : n_rows;
   if (item >= n_items) return;
 
-  int64_t row, eb, ee;
-  bool split = false;
-  if (use_plan) {
-    const int32_t ir = plan.item_row[item];
-    row = ir & 0x7fffffff;
-    eb = plan.item_beg[item];
-    ee = plan.item_end[item];
-    split = ir < 0;
-  } else {
-    row = item;
-    eb = indptr[row];
-    ee = indptr[row + 1];
-  }
+  const auto [row, eb, ee, split] = work_item(indptr, plan, use_plan, item);
   const int sub = (LPE == kWave) ? 0 : lane / LPE;
   const int cl = (LPE == kWave) ? lane : lane % LPE;
   const float scale = (row_scale != nullptr && !split) ? row_scale[row] : 1.f;
@@ -407,14 +445,8 @@ k_aggregate(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indi
     bool cval[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      const int c = c0 + (v * LPE + cl) * VW;
-      cval[v] = c < F;
-      int cc = cval[v] ? c : 0;
-      lo[v] = 0;
-      if constexpr (VW == 8) {  // 16-B bf16 pieces, F % 4 == 0: the last lane's piece starts 4 early
-        if (cval[v] && cc + VW > F) { lo[v] = cc + VW - F; cc -= lo[v]; }  // (its first lo sums unused)
-      }
-      col[v] = cc;
+      const Piece p = piece_at<VW>(c0 + (v * LPE + cl) * VW, F);
+      col[v] = p.col; lo[v] = p.lo; cval[v] = p.valid;
       hcol[v] = (WMODE == WM_HEAD) ? col[v] / gsz : 0;
     }
     float acc[NV][VW];
@@ -466,17 +498,7 @@ k_aggregate(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indi
             }
             continue;
           }
-          int64_t xr;
-          if (XMODE == XM_EDGE) {
-            xr = e0 + jj;
-          } else if (x_is_row) {
-            xr = row;
-          } else if (LPE == kWave) {
-            xr = __builtin_amdgcn_readlane(idxv, jj);
-          } else {
-            xr = __shfl(idxv, jj);
-          }
-          const TX* xp = x + xr * ldx;
+          const TX* xp = x + gather_row<LPE, XMODE>(e0, jj, row, x_is_row, idxv) * ldx;
 #pragma unroll
           for (int v = 0; v < NV; ++v) load_row(xv[u][v], xp + col[v]);
           if (WMODE == WM_HEAD) {
@@ -536,7 +558,8 @@ k_aggregate(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indi
       for (int v = 0; v < NV; ++v) {
         if (!cval[v]) continue;
         Vec<VW> o;
-        // a piece whose first lo sums belong to the lane before: store its upper half only
+        // store_piece's rule, written out as a lambda: with the helper inlined here the compiler
+        // packs the edge loop's adds and multiplies differently (the 16-B form's came out scalar)
         auto put = [&](float* p) {
           if constexpr (VW == 8) {
             if (lo[v]) { *reinterpret_cast<float4*>(p + 4) = make_float4(o.v[4], o.v[5], o.v[6], o.v[7]); return; }
@@ -582,11 +605,10 @@ k_aggregate(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indi
 
 // ---------------------------------------------------------------------------
 // K2' reduce: the gather whose COMP_TYPE is MAX or MIN (gta_reduce).
-//   k_aggregate's generic form -- one wavefront per work item, LPE lanes per edge, 64 source
-//   indices per coalesced load with the next block prefetched, U row loads in flight, masked
-//   columns -- with the reducer in place of the fma: idle edge slots and the < STEP remainder hold
-//   the identity (-inf), the LPE < 64 butterfly folds with the reducer, split rows write their
-//   partial maxima and k_reduce_combine folds them (any order gives the same value).
+//   k_aggregate's generic form (its work_item, piece_at, gather_row and store_piece) with the
+//   reducer in place of the fma: idle edge slots and the < STEP remainder hold the identity (-inf),
+//   the LPE < 64 butterfly folds with the reducer, split rows write their partial maxima and
+//   k_reduce_combine folds them (any order gives the same value).
 //   MIN runs as -max(-x): sbit (0 or the sign bit, wave-uniform) flips every value on its way in
 //   and the result on its way out, which is exact, so one instantiation serves both.
 //   red_max propagates NaN (an explicit compare-and-select plus the unordered test; fmaxf would
@@ -611,19 +633,7 @@ k_reduce(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices
   const int64_t n_items = use_plan ? plan.hdr[0] : n_rows;
   if (item >= n_items) return;
 
-  int64_t row, eb, ee;
-  bool split = false;
-  if (use_plan) {
-    const int32_t ir = plan.item_row[item];
-    row = ir & 0x7fffffff;
-    eb = plan.item_beg[item];
-    ee = plan.item_end[item];
-    split = ir < 0;
-  } else {
-    row = item;
-    eb = indptr[row];
-    ee = indptr[row + 1];
-  }
+  const auto [row, eb, ee, split] = work_item(indptr, plan, use_plan, item);
   const bool empty = eb >= ee;  // a whole row without edges (an item of a split row is never empty)
   const int sub = (LPE == kWave) ? 0 : lane / LPE;
   const int cl = (LPE == kWave) ? lane : lane % LPE;
@@ -633,14 +643,8 @@ k_reduce(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices
     bool cval[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      const int c = c0 + (v * LPE + cl) * VW;
-      cval[v] = c < F;
-      int cc = cval[v] ? c : 0;
-      lo[v] = 0;
-      if constexpr (VW == 8) {  // 16-B bf16 pieces, F % 4 == 0: the last lane's piece starts 4 early
-        if (cval[v] && cc + VW > F) { lo[v] = cc + VW - F; cc -= lo[v]; }
-      }
-      col[v] = cc;
+      const Piece p = piece_at<VW>(c0 + (v * LPE + cl) * VW, F);
+      col[v] = p.col; lo[v] = p.lo; cval[v] = p.valid;
     }
     float acc[NV][VW];
 #pragma unroll
@@ -663,17 +667,7 @@ k_reduce(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices
           const int j = s + u * EPI + sub;
           valid[u] = j < n;
           const int jj = j < n ? j : n - 1;
-          int64_t xr;
-          if (XMODE == XM_EDGE) {
-            xr = e0 + jj;
-          } else if (x_is_row) {
-            xr = row;
-          } else if (LPE == kWave) {
-            xr = __builtin_amdgcn_readlane(idxv, jj);
-          } else {
-            xr = __shfl(idxv, jj);
-          }
-          const TX* xp = x + xr * ldx;
+          const TX* xp = x + gather_row<LPE, XMODE>(e0, jj, row, x_is_row, idxv) * ldx;
 #pragma unroll
           for (int v = 0; v < NV; ++v) load_row(xv[u][v], xp + col[v]);
         }
@@ -703,11 +697,7 @@ k_reduce(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices
         // a split item's partial stays in the max domain (k_reduce_combine flips the folded value)
 #pragma unroll
         for (int k = 0; k < VW; ++k) o.v[k] = split ? acc[v][k] : (empty ? 0.f : red_flip(acc[v][k], sbit));
-        float* p = split ? partial + item * static_cast<int64_t>(F) + col[v] : y + row * ldy + col[v];
-        if constexpr (VW == 8) {  // a piece whose first lo values belong to the lane before: its upper half only
-          if (lo[v]) { *reinterpret_cast<float4*>(p + 4) = make_float4(o.v[4], o.v[5], o.v[6], o.v[7]); continue; }
-        }
-        o.store(p);
+        store_piece(o, split ? partial + item * static_cast<int64_t>(F) + col[v] : y + row * ldy + col[v], lo[v]);
       }
     }
   }
@@ -763,42 +753,16 @@ __device__ __forceinline__ void bcast_all(const float* wa, float* out) {
   }
 }
 
-struct SegItem {  // one (column block, row) work item of the blocked plan: 16 B, loaded with one dwordx4
-  int64_t beg;
-  int32_t row;
-  int32_t len;
-};
-
+// acc[VW] = the lean sum over edges [eb, ee) of lane's VW columns (k_agg_lean, k_agg_seg2d)
 template <int VW, int GL>
-__global__ void __launch_bounds__(kBlock)
-k_agg_lean(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows, PlanView plan,
-           int use_plan, int64_t chunk, const float* __restrict__ x, int64_t ldx, int F,
-           const float* __restrict__ w, int64_t ldw, const float* __restrict__ row_scale,
-           float* __restrict__ y, int64_t ldy, int accumulate, float* __restrict__ partial,
-           const float* __restrict__ xs = nullptr, int64_t ldxs = 0, const float* __restrict__ self_scale = nullptr) {
+__device__ __forceinline__ void lean_gather_sum(const int32_t* __restrict__ indices, int64_t eb, int64_t ee,
+                                                const float* __restrict__ x, int64_t ldx,
+                                                const float* __restrict__ w, int64_t ldw, int lane, float (&acc)[VW]) {
   constexpr int U = (GL > 8) ? GL : 8;               // edges per unrolled step
   constexpr int NWL = (GL > 0) ? U / GL : 0;         // weight loads per step
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t item = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
-  const int64_t n_items = use_plan ? plan.hdr[0] : n_rows;
-  if (item >= n_items) return;
-  int64_t row, eb, ee;
-  bool split = false;
-  if (use_plan) {
-    const int32_t ir = plan.item_row[item];
-    row = ir & 0x7fffffff;
-    eb = plan.item_beg[item];
-    ee = plan.item_end[item];
-    split = ir < 0;
-  } else {
-    row = item;
-    eb = indptr[row];
-    ee = indptr[row + 1];
-  }
   const int col = lane * VW;
   const int head = (GL > 0) ? lane / GL : 0;      // this lane's head (F/H = GL * VW columns)
   const int gsub = (GL > 0) ? lane % GL : 0;      // which edge of a GL-block this lane loads the weight of
-  float acc[VW];
 #pragma unroll
   for (int k = 0; k < VW; ++k) acc[k] = 0.f;
 
@@ -841,6 +805,29 @@ k_agg_lean(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indic
     }
     idxv = idxn;
   }
+}
+
+struct SegItem {  // one (column block, row) work item of the blocked plan: 16 B, loaded with one dwordx4
+  int64_t beg;
+  int32_t row;
+  int32_t len;
+};
+
+template <int VW, int GL>
+__global__ void __launch_bounds__(kBlock)
+k_agg_lean(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows, PlanView plan,
+           int use_plan, int64_t chunk, const float* __restrict__ x, int64_t ldx, int F,
+           const float* __restrict__ w, int64_t ldw, const float* __restrict__ row_scale,
+           float* __restrict__ y, int64_t ldy, int accumulate, float* __restrict__ partial,
+           const float* __restrict__ xs = nullptr, int64_t ldxs = 0, const float* __restrict__ self_scale = nullptr) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t item = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  const int64_t n_items = use_plan ? plan.hdr[0] : n_rows;
+  if (item >= n_items) return;
+  const auto [row, eb, ee, split] = work_item(indptr, plan, use_plan, item);
+  const int col = lane * VW;
+  float acc[VW];
+  lean_gather_sum<VW, GL>(indices, eb, ee, x, ldx, w, ldw, lane, acc);
   Vec<VW> o;
   if (split) {
 #pragma unroll
@@ -854,7 +841,8 @@ k_agg_lean(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indic
       old.load(yp);
 #pragma unroll
       for (int k = 0; k < VW; ++k) o.v[k] = old.v[k] + scale * acc[k];
-    } else if (xs != nullptr) {  // gta_aggregate_self's term, as k_aggregate forms it
+    } else if (xs != nullptr) {  // gta_aggregate_self's term, as k_aggregate forms it (written out in
+      // both kernels: behind a shared helper the compiler contracts `old + scale * acc` differently)
 #pragma clang fp contract(off)
       Vec<VW> sv;
       sv.load(xs + row * ldxs + col);
@@ -891,19 +879,7 @@ k_agg_expr(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indic
   const int64_t item = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
   const int64_t n_items = use_plan ? plan.hdr[0] : n_rows;
   if (item >= n_items) return;
-  int64_t row, eb, ee;
-  bool split = false;
-  if (use_plan) {
-    const int32_t ir = plan.item_row[item];
-    row = ir & 0x7fffffff;
-    eb = plan.item_beg[item];
-    ee = plan.item_end[item];
-    split = ir < 0;
-  } else {
-    row = item;
-    eb = indptr[row];
-    ee = indptr[row + 1];
-  }
+  const auto [row, eb, ee, split] = work_item(indptr, plan, use_plan, item);
   const int col = lane * VW;
   const float* base[NL];
   int64_t ld[NL];
@@ -975,63 +951,17 @@ __global__ void __launch_bounds__(kBlock)
 k_agg_seg2d(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p,
             const float* __restrict__ x, int64_t ldx, const float* __restrict__ w, int64_t ldw,
             float* __restrict__ slabs, const SegItem* __restrict__ items) {
-  constexpr int U = (GL > 8) ? GL : 8;
-  constexpr int NWL = (GL > 0) ? U / GL : 0;
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t k = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
   if (k >= *n_items_p) return;
   const SegItem it = items[k];
   if (it.len == 0) return;
-  const int64_t eb = it.beg, ee = it.beg + it.len;
-  const int col = lane * VW;
-  const int head = (GL > 0) ? lane / GL : 0;
-  const int gsub = (GL > 0) ? lane % GL : 0;
   float acc[VW];
-#pragma unroll
-  for (int q = 0; q < VW; ++q) acc[q] = 0.f;
-  int idxv = indices[min(eb + lane, ee - 1)];
-  for (int64_t e0 = eb; e0 < ee; e0 += kWave) {
-    const int n = static_cast<int>(min<int64_t>(kWave, ee - e0));
-    const int idxn = indices[min(e0 + kWave + lane, ee - 1)];
-    const float* wblk = (GL > 0) ? w + e0 * ldw : nullptr;
-    int s = 0;
-    for (; s + U <= n; s += U) {
-      Vec<VW> xv[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t xr = __builtin_amdgcn_readlane(idxv, s + u);
-        xv[u].load(x + xr * ldx + col);
-      }
-      if (GL > 0) {
-        float wa[NWL > 0 ? NWL : 1], wu[U];
-#pragma unroll
-        for (int q = 0; q < NWL; ++q) wa[q] = wblk[static_cast<int64_t>(s + q * GL + gsub) * ldw + head];
-        bcast_all<(GL > 0 ? GL : 1), U>(wa, wu);
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-          for (int q = 0; q < VW; ++q) acc[q] = fmaf(wu[u], xv[u].v[q], acc[q]);
-      } else {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-          for (int q = 0; q < VW; ++q) acc[q] += xv[u].v[q];
-      }
-    }
-    for (; s < n; ++s) {
-      const int64_t xr = __builtin_amdgcn_readlane(idxv, s);
-      Vec<VW> xv;
-      xv.load(x + xr * ldx + col);
-      const float wv = (GL > 0) ? wblk[static_cast<int64_t>(s) * ldw + head] : 1.f;
-#pragma unroll
-      for (int q = 0; q < VW; ++q) acc[q] = (GL > 0) ? fmaf(wv, xv.v[q], acc[q]) : acc[q] + xv.v[q];
-    }
-    idxv = idxn;
-  }
+  lean_gather_sum<VW, GL>(indices, it.beg, it.beg + it.len, x, ldx, w, ldw, lane, acc);
   Vec<VW> o;
 #pragma unroll
   for (int q = 0; q < VW; ++q) o.v[q] = acc[q];
-  o.store(slabs + k * (kWave * VW) + col);
+  o.store(slabs + k * (kWave * VW) + lane * VW);
 }
 
 // Quarter-wave form of k_agg_seg2d: a wave runs FOUR consecutive (block, row) items,
@@ -4155,35 +4085,42 @@ bool dispatch_x(int xm, int wm, bool bf, const AggArgs& a, int64_t nb, hipStream
 // the 16-B bf16 form (VW = 8): indexed gathers, unweighted or one weight per edge (GIN's sum), one
 // piece per lane; ur: row loads in flight per lane per unrolled step (4: 16 rows per wave at 4 edges
 // per instruction, 8: 32)
-template <int UR, int WM>
-bool dispatch_bf16_vw8_ur(int lpe, const AggArgs& a, int64_t nb, hipStream_t s) {
-  switch (lpe) {
-    case 64: launch_agg<64, 8, 1, XM_IDX, WM, uint16_t, UR>(a, nb, s); return true;
-    case 32: launch_agg<32, 8, 1, XM_IDX, WM, uint16_t, UR>(a, nb, s); return true;
-    case 16: launch_agg<16, 8, 1, XM_IDX, WM, uint16_t, UR>(a, nb, s); return true;
-    case 8: launch_agg<8, 8, 1, XM_IDX, WM, uint16_t, UR>(a, nb, s); return true;
-    case 4: launch_agg<4, 8, 1, XM_IDX, WM, uint16_t, UR>(a, nb, s); return true;
+template <int LPE>
+bool dispatch_bf16_vw8(int ur, int wm, const AggArgs& a, int64_t nb, hipStream_t s) {
+  if (wm == WM_EDGE1) {
+    if (ur == 8) launch_agg<LPE, 8, 1, XM_IDX, WM_EDGE1, uint16_t, 8>(a, nb, s);
+    else launch_agg<LPE, 8, 1, XM_IDX, WM_EDGE1, uint16_t, 4>(a, nb, s);
+  } else {
+    if (ur == 8) launch_agg<LPE, 8, 1, XM_IDX, WM_NONE, uint16_t, 8>(a, nb, s);
+    else launch_agg<LPE, 8, 1, XM_IDX, WM_NONE, uint16_t, 4>(a, nb, s);
   }
-  return false;
-}
-bool dispatch_bf16_vw8(int lpe, int ur, int wm, const AggArgs& a, int64_t nb, hipStream_t s) {
-  if (wm == WM_EDGE1)
-    return ur == 8 ? dispatch_bf16_vw8_ur<8, WM_EDGE1>(lpe, a, nb, s) : dispatch_bf16_vw8_ur<4, WM_EDGE1>(lpe, a, nb, s);
-  return ur == 8 ? dispatch_bf16_vw8_ur<8, WM_NONE>(lpe, a, nb, s) : dispatch_bf16_vw8_ur<4, WM_NONE>(lpe, a, nb, s);
+  return true;
 }
 
-template <int VW>
-bool dispatch_lpe(int lpe, int nv, int xm, int wm, bool bf, const AggArgs& a, int64_t nb, hipStream_t s) {
+// The generic forms' ladder (k_aggregate, k_reduce): fn(VW, LPE, NV) as integral constants.  64 lanes
+// per edge take 1, 2 or 4 pieces per lane (the 16-B bf16 form: 1), fewer lanes one.
+template <int N>
+using IC = std::integral_constant<int, N>;
+
+template <int VW, class Fn>
+bool dispatch_lpe(int lpe, int nv, Fn fn) {
   switch (lpe) {
     case 64:
-      if (nv == 1) return dispatch_x<64, VW, 1>(xm, wm, bf, a, nb, s);
-      if (nv == 2) return dispatch_x<64, VW, 2>(xm, wm, bf, a, nb, s);
-      return dispatch_x<64, VW, 4>(xm, wm, bf, a, nb, s);
-    case 32: return dispatch_x<32, VW, 1>(xm, wm, bf, a, nb, s);
-    case 16: return dispatch_x<16, VW, 1>(xm, wm, bf, a, nb, s);
-    case 8: return dispatch_x<8, VW, 1>(xm, wm, bf, a, nb, s);
-    default: return dispatch_x<4, VW, 1>(xm, wm, bf, a, nb, s);
+      if constexpr (VW < 8) {
+        if (nv == 2) return fn(IC<VW>{}, IC<64>{}, IC<2>{});
+        if (nv != 1) return fn(IC<VW>{}, IC<64>{}, IC<4>{});
+      }
+      return fn(IC<VW>{}, IC<64>{}, IC<1>{});
+    case 32: return fn(IC<VW>{}, IC<32>{}, IC<1>{});
+    case 16: return fn(IC<VW>{}, IC<16>{}, IC<1>{});
+    case 8: return fn(IC<VW>{}, IC<8>{}, IC<1>{});
+    default: return fn(IC<VW>{}, IC<4>{}, IC<1>{});
   }
+}
+
+template <class Fn>
+bool dispatch_vw(int vw, int lpe, int nv, Fn fn) {  // VW 4, 2 or 1
+  return vw == 4 ? dispatch_lpe<4>(lpe, nv, fn) : (vw == 2 ? dispatch_lpe<2>(lpe, nv, fn) : dispatch_lpe<1>(lpe, nv, fn));
 }
 
 // Tuning knobs (gta_debug_set / gta_tuning_*): per calling THREAD, or per stream when a knob set
@@ -4380,6 +4317,63 @@ int gta_aggregate_plan_build(const int64_t* indptr, int64_t n_rows, int64_t nnz,
 
 }  // extern "C"
 namespace {
+// The generic gather forms' shape for rows of F elements (aggregate_impl, reduce_impl).  vw: the
+// widest vector at which every access stays aligned (ok_vw, the caller's layout test); one edge
+// per wave instruction (LPE = 64, wave-uniform row base) whenever the row fills 64 lanes at
+// >= 8 B/lane: measured 3 % faster than two edges per instruction at float4 for F = 128
+// (profiles/r01_agg_sweep_1.json).  lpe_knob: the caller honours agg_lpe at F = 128.
+// vw8: bf16 rows gathered in 16-B pieces (8 elements per lane, the last lane's piece clamped
+// inside the row) where the caller's layout admits them (vw8_ok): half the gather instructions of
+// 8-B pieces for the same rows (GIN products' 200-B rows: 13 lanes, 4 edges per wave instruction).
+struct GatherShape {
+  int vw, lpe, nv;
+  bool vw8;
+};
+
+template <class OkVw>
+GatherShape gather_shape(int64_t F, bool bf, OkVw ok_vw, bool lpe_knob, bool vw8_ok) {
+  const Tuning& t = tuning();
+  GatherShape g{ok_vw(4) ? 4 : (ok_vw(2) ? 2 : 1), 4, 1, false};
+  if (t.force_vw && t.force_vw <= g.vw && ok_vw(t.force_vw)) g.vw = t.force_vw;
+  if (!bf && g.vw == 4 && F < 4 * kWave && F >= 2 * kWave && ok_vw(2)) g.vw = 2;
+  g.vw8 = bf && t.agg_bf16_vw8 && F % 4 == 0 && F >= 8 && F <= 512 && vw8_ok;
+  if (g.vw8) g.vw = 8;  // at most 64 lanes, one piece each
+  const int64_t lanes = (F + g.vw - 1) / g.vw;
+  if (lanes >= kWave) {
+    g.lpe = kWave;
+    g.nv = lanes >= 4 * kWave ? 4 : (lanes > kWave ? 2 : 1);
+  } else {
+    while (g.lpe < lanes) g.lpe <<= 1;
+  }
+  if (lpe_knob && !bf && t.force_lpe == 32 && F == 128 && ok_vw(4)) g = {4, 32, 1, false};
+  if (lpe_knob && !bf && t.force_lpe == 64 && F == 128 && ok_vw(2)) g = {2, 64, 1, false};
+  return g;
+}
+
+// the arguments every per-row gather kernel takes; returns the bound on its work items (the rows,
+// or what the plan can hold), or fail()'s code
+int64_t gather_args(AggArgs& a, const char* who, const int64_t* indptr, const int32_t* indices, int64_t n_rows,
+                    int64_t nnz, int x_mode, const void* x, int64_t ldx, int64_t F, float* y, int64_t ldy,
+                    const void* plan, int64_t plan_chunk, void* workspace) {
+  a.indptr = indptr; a.indices = indices; a.n_rows = n_rows;
+  a.use_plan = plan != nullptr; a.chunk = plan_chunk; a.x_is_row = (x_mode == GTA_IDX_DST);
+  a.x = x; a.ldx = ldx; a.F = static_cast<int>(F); a.y = y; a.ldy = ldy;
+  a.partial = static_cast<float*>(workspace);
+  if (!plan) return n_rows;
+  if (plan_chunk <= 0 || !workspace) return fail(GTA_ERR_ARG, std::string(who) + ": plan needs chunk and workspace");
+  const int64_t bound = max_items_for(n_rows, nnz, plan_chunk);
+  a.plan = plan_view(const_cast<void*>(plan), n_rows, bound);
+  return bound;
+}
+
+// the combine launch over a plan's split rows (at most one per chunk of edges), if there can be any
+template <class Launch>
+bool launch_combine(int64_t nnz, int64_t plan_chunk, Launch launch) {
+  const int64_t sb = (nnz + plan_chunk - 1) / plan_chunk;  // >= number of split rows
+  if (sb > 0) launch(dim3(static_cast<unsigned>((sb + kWavesPerBlock - 1) / kWavesPerBlock)));
+  return sb > 0;
+}
+
 int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
                    const void* x, int64_t ldx, int64_t F, int x_dtype, const float* w, int64_t ldw, int64_t heads,
                    const float* row_scale, float* y, int64_t ldy, int accumulate, const void* plan,
@@ -4434,37 +4428,11 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
     if (wm == WM_FULL && (ldw % vw || !aligned(w, 4 * vw))) return false;
     return true;
   };
-  int vw = ok_vw(4) ? 4 : (ok_vw(2) ? 2 : 1);
-  if (tuning().force_vw && tuning().force_vw <= vw && ok_vw(tuning().force_vw)) vw = tuning().force_vw;
-  // one edge per wave instruction (LPE = 64, wave-uniform row base) whenever the
-  // row fills 64 lanes at >= 8 B/lane: measured 3 % faster than two edges per
-  // instruction at float4 for F = 128 (profiles/r01_agg_sweep_1.json)
-  if (!bf && vw == 4 && F < 4 * kWave && F >= 2 * kWave && ok_vw(2)) vw = 2;
-  const int64_t lanes = (F + vw - 1) / vw;
-  int lpe, nv = 1;
-  if (lanes >= kWave) {
-    lpe = kWave;
-    nv = lanes >= 4 * kWave ? 4 : (lanes > kWave ? 2 : 1);
-  } else {
-    lpe = 4;
-    while (lpe < lanes) lpe <<= 1;
-  }
-  if (!bf && tuning().force_lpe == 32 && F == 128 && ok_vw(4)) { lpe = 32; vw = 4; nv = 1; }
-  if (!bf && tuning().force_lpe == 64 && F == 128 && ok_vw(2)) { lpe = 64; vw = 2; nv = 1; }
-  // bf16 rows gathered in 16-B pieces (8 elements per lane, the last lane's piece clamped inside
-  // the row): half the gather instructions of 8-B pieces for the same rows (GIN products' 200-B
-  // rows: 13 lanes, 4 edges per wave instruction)
-  bool vw8 = false;
-  if (bf && tuning().agg_bf16_vw8 && (wm == WM_NONE || wm == WM_EDGE1) && xm == XM_IDX && F % 4 == 0 && F >= 8 && F <= 512 &&
-      ldx % 4 == 0 && aligned(x, 8) && (!xs || (ldxs % 4 == 0 && aligned(xs, 8))) &&
-      (y_bf16 ? (ldy % 4 == 0 && aligned(y, 8)) : (ldy % 4 == 0 && aligned(y, 16)))) {
-    const int64_t ln = (F + 7) / 8;
-    vw8 = true;
-    vw = 8;
-    nv = 1;
-    lpe = 4;
-    while (lpe < ln) lpe <<= 1;
-  }
+  // the 16-B bf16 form: unweighted or one weight per edge, indexed, xs and y (fp32 or bf16) aligned to it
+  const bool vw8_ok = (wm == WM_NONE || wm == WM_EDGE1) && xm == XM_IDX && ldx % 4 == 0 && aligned(x, 8) &&
+                      (!xs || (ldxs % 4 == 0 && aligned(xs, 8))) && ldy % 4 == 0 && aligned(y, y_bf16 ? 8 : 16);
+  const GatherShape g = gather_shape(F, bf, ok_vw, /*lpe_knob=*/true, vw8_ok);
+  const int vw = g.vw, lpe = g.lpe, nv = g.nv;
 
   if (ex) {
     const int nl = ex_mode == XM_EX1 ? (ex_bin(exa.code, 0) == GTA_BIN_NONE ? 1 : 2) : (ex_mode == XM_EX2 ? 3 : 4);
@@ -4473,19 +4441,12 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
         return fail(GTA_ERR_UNSUPPORTED, "aggregate_expr: an operand's rows are not aligned to the gather's vector width");
   }
   AggArgs a{};
+  const int64_t bound = gather_args(a, "aggregate", indptr, indices, n_rows, nnz, x_mode, x, ldx, F, y, ldy, plan,
+                                    plan_chunk, workspace);
+  if (bound < 0) return static_cast<int>(bound);
   a.ex = exa;
-  a.indptr = indptr; a.indices = indices; a.n_rows = n_rows;
-  a.use_plan = plan != nullptr; a.chunk = plan_chunk; a.x_is_row = (x_mode == GTA_IDX_DST);
-  a.x = x; a.ldx = ldx; a.F = static_cast<int>(F); a.w = w; a.ldw = ldw; a.gsz = gsz;
-  a.row_scale = row_scale; a.y = y; a.ldy = ldy; a.accumulate = accumulate;
-  a.partial = static_cast<float*>(workspace);
+  a.w = w; a.ldw = ldw; a.gsz = gsz; a.row_scale = row_scale; a.accumulate = accumulate;
   a.xs = xs; a.ldxs = ldxs; a.self_scale = self_scale; a.y_bf16 = y_bf16;
-  int64_t bound = n_rows;
-  if (plan) {
-    if (plan_chunk <= 0 || !workspace) return fail(GTA_ERR_ARG, "aggregate: plan needs chunk and workspace");
-    bound = max_items_for(n_rows, nnz, plan_chunk);
-    a.plan = plan_view(const_cast<void*>(plan), n_rows, bound);
-  }
   hipStream_t s = S(stream);
   bool ok = false;
   // lean path: one edge per instruction exactly filling the wave, SpMM form
@@ -4533,24 +4494,20 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
 #undef GTA_EXPR
     ok = true;
   }
-  if (!ok && vw8) ok = dispatch_bf16_vw8(lpe, tuning().agg_bf16_vw8, wm, a, bound, s);
-  if (!ok) switch (vw) {
-    case 8: break;
-    case 4: ok = dispatch_lpe<4>(lpe, nv, xm, wm, bf, a, bound, s); break;
-    case 2: ok = dispatch_lpe<2>(lpe, nv, xm, wm, bf, a, bound, s); break;
-    default: ok = dispatch_lpe<1>(lpe, nv, xm, wm, bf, a, bound, s); break;
+  if (!ok && g.vw8) {
+    ok = dispatch_lpe<8>(lpe, 1, [&](auto, auto L, auto) {
+      return dispatch_bf16_vw8<L()>(tuning().agg_bf16_vw8, wm, a, bound, s);
+    });
+  } else if (!ok) {
+    ok = dispatch_vw(vw, lpe, nv, [&](auto V, auto L, auto N) { return dispatch_x<L(), V(), N()>(xm, wm, bf, a, bound, s); });
   }
   if (!ok) return fail(GTA_ERR_UNSUPPORTED, "aggregate: no kernel variant");
   GTA_LAUNCHED("k_aggregate");
-  if (plan) {
-    const int64_t sb = (nnz + plan_chunk - 1) / plan_chunk;  // >= number of split rows
-    if (sb > 0) {
-      const int64_t blocks = (sb + kWavesPerBlock - 1) / kWavesPerBlock;
-      k_aggregate_combine<<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(
-          a.plan, a.F, row_scale, y, ldy, accumulate, a.partial, xs, ldxs, bf ? 1 : 0, self_scale, y_bf16);
-      GTA_LAUNCHED("k_aggregate_combine");
-    }
-  }
+  const bool combined = plan && launch_combine(nnz, plan_chunk, [&](dim3 grid) {
+    k_aggregate_combine<<<grid, dim3(kBlock), 0, s>>>(a.plan, a.F, row_scale, y, ldy, accumulate, a.partial, xs, ldxs,
+                                                      bf ? 1 : 0, self_scale, y_bf16);
+  });
+  if (combined) GTA_LAUNCHED("k_aggregate_combine");
   return GTA_OK;
 }
 
@@ -4576,31 +4533,6 @@ bool dispatch_red_x(int xm, bool bf, const AggArgs& a, uint32_t sbit, int64_t nb
   return true;
 }
 
-template <int VW>
-bool dispatch_red_lpe(int lpe, int nv, int xm, bool bf, const AggArgs& a, uint32_t sbit, int64_t nb, hipStream_t s) {
-  switch (lpe) {
-    case 64:
-      if (nv == 1) return dispatch_red_x<64, VW, 1>(xm, bf, a, sbit, nb, s);
-      if (nv == 2) return dispatch_red_x<64, VW, 2>(xm, bf, a, sbit, nb, s);
-      return dispatch_red_x<64, VW, 4>(xm, bf, a, sbit, nb, s);
-    case 32: return dispatch_red_x<32, VW, 1>(xm, bf, a, sbit, nb, s);
-    case 16: return dispatch_red_x<16, VW, 1>(xm, bf, a, sbit, nb, s);
-    case 8: return dispatch_red_x<8, VW, 1>(xm, bf, a, sbit, nb, s);
-    default: return dispatch_red_x<4, VW, 1>(xm, bf, a, sbit, nb, s);
-  }
-}
-
-bool dispatch_red_vw8(int lpe, const AggArgs& a, uint32_t sbit, int64_t nb, hipStream_t s) {
-  switch (lpe) {
-    case 64: launch_red<64, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
-    case 32: launch_red<32, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
-    case 16: launch_red<16, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
-    case 8: launch_red<8, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
-    case 4: launch_red<4, 8, 1, XM_IDX, uint16_t>(a, sbit, nb, s); return true;
-  }
-  return false;
-}
-
 int reduce_impl(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
                 const void* x, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy, const void* plan,
                 int64_t plan_chunk, void* workspace, void* stream) {
@@ -4623,60 +4555,30 @@ int reduce_impl(int red, const int64_t* indptr, const int32_t* indices, int64_t 
   auto ok_vw = [&](int vw) {
     return !(F % vw || ldx % vw || ldy % vw || !aligned(x, xe * vw) || !aligned(y, 4 * vw));
   };
-  int vw = ok_vw(4) ? 4 : (ok_vw(2) ? 2 : 1);
-  if (tuning().force_vw && tuning().force_vw <= vw && ok_vw(tuning().force_vw)) vw = tuning().force_vw;
-  // one edge per wave instruction whenever the row fills 64 lanes at >= 8 B per lane (as the aggregate)
-  if (!bf && vw == 4 && F < 4 * kWave && F >= 2 * kWave && ok_vw(2)) vw = 2;
-  const int64_t lanes = (F + vw - 1) / vw;
-  int lpe, nv = 1;
-  if (lanes >= kWave) {
-    lpe = kWave;
-    nv = lanes >= 4 * kWave ? 4 : (lanes > kWave ? 2 : 1);
-  } else {
-    lpe = 4;
-    while (lpe < lanes) lpe <<= 1;
-  }
-  // bf16 rows in 16-B pieces (8 elements per lane, the last lane's piece clamped inside the row)
-  bool vw8 = false;
-  if (bf && nnz > 0 && tuning().agg_bf16_vw8 && !tuning().force_vw && F % 4 == 0 && F >= 8 && F <= 512 && ldx % 4 == 0 &&
-      aligned(x, 8) && ldy % 4 == 0 && aligned(y, 16)) {
-    const int64_t ln = (F + 7) / 8;
-    vw8 = true;
-    vw = 8;
-    nv = 1;
-    lpe = 4;
-    while (lpe < ln) lpe <<= 1;
-  }
+  // the 16-B bf16 form: only with edges to read (x is y's fp32 rows otherwise) and no agg_vw knob
+  const bool vw8_ok = nnz > 0 && !tuning().force_vw && ldx % 4 == 0 && aligned(x, 8) && ldy % 4 == 0 && aligned(y, 16);
+  const GatherShape g = gather_shape(F, bf, ok_vw, /*lpe_knob=*/false, vw8_ok);
   AggArgs a{};
-  a.indptr = indptr; a.indices = indices; a.n_rows = n_rows;
-  a.use_plan = plan != nullptr; a.chunk = plan_chunk; a.x_is_row = (x_mode == GTA_IDX_DST);
-  a.x = x; a.ldx = ldx; a.F = static_cast<int>(F); a.y = y; a.ldy = ldy;
-  a.partial = static_cast<float*>(workspace);
-  int64_t bound = n_rows;
-  if (plan) {
-    if (plan_chunk <= 0 || !workspace) return fail(GTA_ERR_ARG, "reduce: plan needs chunk and workspace");
-    bound = max_items_for(n_rows, nnz, plan_chunk);
-    a.plan = plan_view(const_cast<void*>(plan), n_rows, bound);
-  }
+  const int64_t bound = gather_args(a, "reduce", indptr, indices, n_rows, nnz, x_mode, x, ldx, F, y, ldy, plan,
+                                    plan_chunk, workspace);
+  if (bound < 0) return static_cast<int>(bound);
   const uint32_t sbit = red == GTA_RED_MIN ? 0x80000000u : 0u;
   hipStream_t s = S(stream);
-  bool ok = false;
-  if (vw8) ok = dispatch_red_vw8(lpe, a, sbit, bound, s);
-  else switch (vw) {
-    case 4: ok = dispatch_red_lpe<4>(lpe, nv, xm, bf, a, sbit, bound, s); break;
-    case 2: ok = dispatch_red_lpe<2>(lpe, nv, xm, bf, a, sbit, bound, s); break;
-    default: ok = dispatch_red_lpe<1>(lpe, nv, xm, bf, a, sbit, bound, s); break;
+  bool ok;
+  if (g.vw8) {
+    ok = dispatch_lpe<8>(g.lpe, 1, [&](auto, auto L, auto) {
+      launch_red<L(), 8, 1, XM_IDX, uint16_t>(a, sbit, bound, s);
+      return true;
+    });
+  } else {
+    ok = dispatch_vw(g.vw, g.lpe, g.nv, [&](auto V, auto L, auto N) { return dispatch_red_x<L(), V(), N()>(xm, bf, a, sbit, bound, s); });
   }
   if (!ok) return fail(GTA_ERR_UNSUPPORTED, "reduce: no kernel variant");
   GTA_LAUNCHED("k_reduce");
-  if (plan) {
-    const int64_t sb = (nnz + plan_chunk - 1) / plan_chunk;  // >= number of split rows
-    if (sb > 0) {
-      const int64_t blocks = (sb + kWavesPerBlock - 1) / kWavesPerBlock;
-      k_reduce_combine<<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(a.plan, a.F, sbit, y, ldy, a.partial);
-      GTA_LAUNCHED("k_reduce_combine");
-    }
-  }
+  const bool combined = plan && launch_combine(nnz, plan_chunk, [&](dim3 grid) {
+    k_reduce_combine<<<grid, dim3(kBlock), 0, s>>>(a.plan, a.F, sbit, y, ldy, a.partial);
+  });
+  if (combined) GTA_LAUNCHED("k_reduce_combine");
   return GTA_OK;
 }
 }  // namespace

@@ -150,6 +150,34 @@ class AggregatePlan:
         return int(self.buf[8:16].view(torch.int64).item())
 
 
+def _gather_operand(graph, x, x_mode, who):
+    """(ldx, x_dt) of the rows a gather reads: float32, or bfloat16 gathered by index."""
+    if x.dtype == torch.bfloat16 and x_mode == "edge":
+        raise TypeError(f"{who}: bfloat16 rows are gathered by index (src / dst)")
+    ldx = _rows(x, "x", torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32)
+    if x_mode == "edge" and x.shape[0] < graph.nnz:
+        raise ValueError("edge-mode x must have E rows")
+    if x_mode == "src" and x.shape[0] < graph.n_cols:
+        raise ValueError("src-mode x must have n_cols rows")
+    if x_mode == "dst" and x.shape[0] < graph.n_rows:
+        raise ValueError("dst-mode x must have n_rows rows")
+    return ldx, _lib.GTA_BF16 if x.dtype == torch.bfloat16 else _lib.GTA_F32
+
+
+def _plan_args(graph, plan, F):
+    """(plan buffer, workspace, chunk) of plan: None, an AggregatePlan, or an int chunk (graph's
+    cached plan, dropped when no row is split: the per-row form, same values, no combine launch)."""
+    if isinstance(plan, int):
+        plan = graph.plan(plan)
+        if plan.splits == 0:
+            plan = None
+    if plan is None:
+        return None, None, 0
+    if plan.graph is not graph:
+        raise ValueError("plan built for another graph")
+    return plan.buf, plan.workspace(F), plan.chunk
+
+
 def aggregate(graph, x, x_mode="src", w=None, row_scale=None, out=None, accumulate=False, plan=None, self_term=None,
               out_dtype=torch.float32):
     """y[i] (+)= row_scale[i] * sum_{e in row i} w(e) * x[idx(e)]  (K6/K7/K2).
@@ -170,16 +198,7 @@ def aggregate(graph, x, x_mode="src", w=None, row_scale=None, out=None, accumula
     """
     _need_gpu(x, w, row_scale, out, graph.indptr)
     F = x.shape[1]
-    if x.dtype == torch.bfloat16 and x_mode == "edge":
-        raise TypeError("aggregate: bfloat16 rows are gathered by index (src / dst)")
-    ldx = _rows(x, "x", torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32)
-    x_dt = _lib.GTA_BF16 if x.dtype == torch.bfloat16 else _lib.GTA_F32
-    if x_mode == "edge" and x.shape[0] < graph.nnz:
-        raise ValueError("edge-mode x must have E rows")
-    if x_mode == "src" and x.shape[0] < graph.n_cols:
-        raise ValueError("src-mode x must have n_cols rows")
-    if x_mode == "dst" and x.shape[0] < graph.n_rows:
-        raise ValueError("dst-mode x must have n_rows rows")
+    ldx, x_dt = _gather_operand(graph, x, x_mode, "aggregate")
     ldw, heads = 0, 0
     if w is not None:
         if w.dim() == 1:
@@ -203,16 +222,7 @@ def aggregate(graph, x, x_mode="src", w=None, row_scale=None, out=None, accumula
         raise ValueError("out must be [N, F]")
     if graph.n_rows == 0:
         return out
-    if isinstance(plan, int):
-        plan = graph.plan(plan)
-        if plan.splits == 0:  # no row is split: the per-row form (same sums, no combine launch)
-            plan = None
-    pbuf = ws = None
-    chunk = 0
-    if plan is not None:
-        if plan.graph is not graph:
-            raise ValueError("plan built for another graph")
-        pbuf, ws, chunk = plan.buf, plan.workspace(F), plan.chunk
+    pbuf, ws, chunk = _plan_args(graph, plan, F)
     if self_term is not None:
         xs, sc = self_term
         if accumulate or xs.dtype != x.dtype or xs.shape[0] < graph.n_rows or xs.shape[1] != F:
@@ -253,16 +263,7 @@ def reduce(graph, x, red="MAX", x_mode="src", out=None, plan=None):
     if x_mode not in _MODES:
         raise ValueError(f"reduce: x_mode must be one of {sorted(_MODES)} (got {x_mode!r})")
     F = x.shape[1]
-    if x.dtype == torch.bfloat16 and x_mode == "edge":
-        raise TypeError("reduce: bfloat16 rows are gathered by index (src / dst)")
-    ldx = _rows(x, "x", torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32)
-    x_dt = _lib.GTA_BF16 if x.dtype == torch.bfloat16 else _lib.GTA_F32
-    if x_mode == "edge" and x.shape[0] < graph.nnz:
-        raise ValueError("edge-mode x must have E rows")
-    if x_mode == "src" and x.shape[0] < graph.n_cols:
-        raise ValueError("src-mode x must have n_cols rows")
-    if x_mode == "dst" and x.shape[0] < graph.n_rows:
-        raise ValueError("dst-mode x must have n_rows rows")
+    ldx, x_dt = _gather_operand(graph, x, x_mode, "reduce")
     if out is None:
         out = torch.empty(graph.n_rows, F, dtype=torch.float32, device=x.device)
     ldy = _rows(out, "out")
@@ -270,16 +271,7 @@ def reduce(graph, x, red="MAX", x_mode="src", out=None, plan=None):
         raise ValueError("out must be [N, F]")
     if graph.n_rows == 0:
         return out
-    if isinstance(plan, int):
-        plan = graph.plan(plan)
-        if plan.splits == 0:  # no row is split: the per-row form (same values, no combine launch)
-            plan = None
-    pbuf = ws = None
-    chunk = 0
-    if plan is not None:
-        if plan.graph is not graph:
-            raise ValueError("plan built for another graph")
-        pbuf, ws, chunk = plan.buf, plan.workspace(F), plan.chunk
+    pbuf, ws, chunk = _plan_args(graph, plan, F)
     check(_L().gta_reduce(_REDS[red], _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz, _MODES[x_mode],
                           _ptr(x), ldx, F, x_dt, _ptr(out), ldy, _ptr(pbuf), chunk, _ptr(ws), _stream(x.device)),
           "reduce")
@@ -328,16 +320,7 @@ def aggregate_expr(graph, shape, operands, bins, sfs=None, swap=False, plan=None
     out = torch.empty(graph.n_rows, F, dtype=torch.float32, device=ts[0].device)
     if graph.n_rows == 0:
         return out
-    if isinstance(plan, int):
-        plan = graph.plan(plan)
-        if plan.splits == 0:  # as aggregate: no split row, the per-row form
-            plan = None
-    pbuf = ws = None
-    chunk = 0
-    if plan is not None:
-        if plan.graph is not graph:
-            raise ValueError("plan built for another graph")
-        pbuf, ws, chunk = plan.buf, plan.workspace(F), plan.chunk
+    pbuf, ws, chunk = _plan_args(graph, plan, F)
     rc = _L().gta_aggregate_expr(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz, n_ops,
                                  ptrs, modes, lds, cb, cs, int(bool(swap)), F, _ptr(out), F, _ptr(pbuf), chunk,
                                  _ptr(ws), _stream(ts[0].device))
