@@ -53,6 +53,12 @@ SIGNATURES = {
     "gta_apply_edge": (_i32, [_i32, _i32, _vp, _vp, _i64, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _vp,
                               _i64, _vp]),
     "gta_edge_softmax": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "gta_softmax_shift": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp]),
+    "gta_edge_softmax_shifted": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp,
+                                        _vp]),
+    "gta_gat_aggregate_blocked_shifted": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64,
+                                                 _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp,
+                                                 _vp]),
     "gta_apply_edge_flat": (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _vp, _i64,
                                    _vp]),
     "gta_apply_node": (_i32, [_i32, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i64, _vp]),

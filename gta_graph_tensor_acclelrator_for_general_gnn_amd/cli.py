@@ -52,6 +52,8 @@ def parser():
     p.add_argument("--heads", type=int, default=16, help="attention heads (GAT)")
     p.add_argument("--aggregator", default="ADD", choices=list(frontend.AGGREGATORS),
                    help="reduce function of the message gathers (their COMP_TYPE); GAT takes ADD only")
+    p.add_argument("--stable-softmax", action="store_true",
+                   help="overflow-safe attention softmax: exp(score - row max) (GAT; off: the unshifted kernels)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--reps", type=int, default=3, help="runs per layer; the fastest is reported")
     p.add_argument("--model-edges", type=int, default=1 << 20,
@@ -75,7 +77,8 @@ def run(args, device, log=print):
                                    getattr(args, "aggregator", "ADD"))
         cands = compiler.search(records, g.n_rows, *meta, pingpang=args.isPingpang, sinput=args.isSinput)
         kw = dict(reorder=args.isReorder, heads=args.heads, metadata=meta, pingpang=args.isPingpang,
-                  sinput=args.isSinput, aggregator=getattr(args, "aggregator", "ADD"))
+                  sinput=args.isSinput, aggregator=getattr(args, "aggregator", "ADD"),
+                  stable_softmax=getattr(args, "stable_softmax", False))
         lay = None
         for k, (op_array, tile_size_list) in enumerate(c[:2] for c in cands):
             try:

@@ -995,6 +995,18 @@ __device__ __forceinline__ int bcast16(int v, int k) {  // lane (l & 0x30) | k, 
   return v;
 }
 
+// Shifted softmax (gta.h, ABI 15 additive): for the exp-form score functions sf = exp . g the
+// weight is v = expf(g(a + b) - m), m = the row's largest g(a + b) (k_softmax_shift), so v <= 1.
+// sf_g is the value sf_apply hands to expf; sf_shift subtracts once in fp32 (never contracted
+// with g's multiply) and exponentiates.
+inline bool sf_is_exp_form(int sf) { return sf == GTA_SF_EXP_LEAKY_RELU || sf == GTA_SF_EXP; }
+__device__ __forceinline__ float sf_g(int sf, float t) { return sf == GTA_SF_EXP ? t : (t > 0.f ? t : 0.2f * t); }
+__device__ __forceinline__ float sf_shift(int sf, float t, float m) {
+#pragma clang fp contract(off)
+  const float g = sf_g(sf, t);
+  return expf(g - m);
+}
+
 // ATT (fused GAT attention, GAT ops 6-12 minus the final SF): the edge weight is
 // not read but computed, v = sf(a[row, h] + b[src, h]) from the two score tables
 // (b gathered like x, from the same column block), and the item's per-head sum of
@@ -1007,12 +1019,14 @@ struct AttArgs {
   int64_t ldb;
   int sf;
   int H;           // the item's per-head sums of v follow its F partials in the slab row (stride F + H padded to 4)
+  const float* shift = nullptr;  // SH: [n_rows, H] contiguous row maxima of g(a + b) (k_softmax_shift)
 };
 
-template <int VW, int U, bool WEIGHTED, int NT = 0, bool ATT = false, int SFC = -1, int G = 16>
+template <int VW, int U, bool WEIGHTED, int NT = 0, bool ATT = false, int SFC = -1, int G = 16, bool SH = false>
 // NT bit 0: non-temporal index/weight loads, bit 1: slab stores; SFC >= 0: the ATT special function
 // fixed at compile time (-1: att.sf at run time); G = lanes per item (16: four items per wave,
-// 32: two items per wave -- one 512-B row per half-wave instruction at F = 128)
+// 32: two items per wave -- one 512-B row per half-wave instruction at F = 128); SH: the ATT
+// weight is the shifted one, expf(g(a + b) - att.shift[row, h])
 __global__ void __launch_bounds__(kBlock)
 k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
            int64_t ldx, const float* __restrict__ w, int64_t ldw, int lph, float* __restrict__ slabs,
@@ -1040,6 +1054,8 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
   for (int q = 0; q < VW; ++q) acc[q] = 0.f;
   float arow = 0.f, ssum = 0.f;
   if (ATT && len > 0) arow = att.a[static_cast<int64_t>(it.row) * att.lda + head];
+  float mrow = 0.f;
+  if (ATT && SH && len > 0) mrow = att.shift[static_cast<int64_t>(it.row) * att.H + head];
   auto ldi = [&](int64_t e) { return (NT & 1) ? __builtin_nontemporal_load(indices + e) : indices[e]; };
   int idxv = (l16 < len) ? ldi(eb + l16) : 0;
   for (int c = 0; c < maxlen; c += G) {
@@ -1059,7 +1075,8 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
           for (int q = 0; q < NQ; ++q) xv[u][q] = p[q];
           if (ATT) {
             const float sv = arow + att.b[static_cast<int64_t>(src) * att.ldb + head];
-            wu[u] = (SFC >= 0) ? sf_apply(SFC, sv) : sf_apply(att.sf, sv);
+            if (SH) wu[u] = (SFC >= 0) ? sf_shift(SFC, sv, mrow) : sf_shift(att.sf, sv, mrow);
+            else wu[u] = (SFC >= 0) ? sf_apply(SFC, sv) : sf_apply(att.sf, sv);
             ssum += wu[u];
           } else if (WEIGHTED) {
             const float* wp = w + (eb + c + s + u) * ldw + head;
@@ -1481,13 +1498,16 @@ k_agg_h32pf(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_i
 // Direct epilogue (row_ptr given): an item that is its row's only item (low-degree rows at
 // small B) writes y (and sums) itself, exactly as the ordered reduce would (0 + p = p), and the
 // reduce skips its row (k_seg_reduce_att with skip_single).
-template <int NT>
+// SH: the shifted weight, v = expf(leaky_relu(a + b) - shift[row, h]); the row's shift is loaded
+// once beside a[row, h], the 2-SF step and the direct epilogue are unchanged.
+template <int NT, bool SH = false>
 __global__ void __launch_bounds__(kBlock)
 k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
           uint32_t row_bytes, const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
           uint32_t brow_bytes, float* __restrict__ slabs, const SegItem* __restrict__ items,
           const int64_t* __restrict__ row_ptr = nullptr, int normalize = 1, float* __restrict__ y = nullptr,
-          int64_t ldy = 0, float* __restrict__ sums = nullptr, int sf_out = GTA_SF_NONE) {
+          int64_t ldy = 0, float* __restrict__ sums = nullptr, int sf_out = GTA_SF_NONE,
+          const float* __restrict__ shift = nullptr) {
   constexpr int G = 32, U = 8, F = 128, LDS = F + 8;
   const int lane = threadIdx.x & (kWave - 1);
   const int l32 = lane & (G - 1);
@@ -1505,13 +1525,14 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   const char* xb = reinterpret_cast<const char*>(x);
   const char* bb = reinterpret_cast<const char*>(b);
   const float arow = (len > 0) ? a[static_cast<int64_t>(it.row) * lda + h] : 0.f;
+  const float mrow = (SH && len > 0) ? shift[static_cast<int64_t>(it.row) * 8 + h] : 0.f;
   auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
   auto row = [&](int src) -> float4 {
     return *reinterpret_cast<const float4*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
   };
   auto score = [&](int src) -> float {
     const float sv = arow + *reinterpret_cast<const float*>(bb + (__umul24(static_cast<uint32_t>(src), brow_bytes) + hb));
-    return sf_apply(GTA_SF_EXP_LEAKY_RELU, sv);
+    return SH ? sf_shift(GTA_SF_EXP_LEAKY_RELU, sv, mrow) : sf_apply(GTA_SF_EXP_LEAKY_RELU, sv);
   };
   const int32_t* ic = indices + it.beg;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -2290,11 +2311,13 @@ k_apply_node4(int bin, int sf, uint32_t n4, uint32_t F4, const TA* __restrict__ 
 // recomputes v (same bits) and writes v / sum -- one contiguous 256-B store per
 // step.  normalize = 0 writes v in pass 1 and skips pass 2.
 // ---------------------------------------------------------------------------
-template <int H>
+// SH: the shifted weight, v = expf(g(a + b) - shift[row, h]) (sf an exp-form, checked by the host).
+template <int H, bool SH = false>
 __global__ void __launch_bounds__(kBlock)
 k_edge_softmax(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
                const float* __restrict__ a, int64_t lda, const float* __restrict__ b, int64_t ldb, int sf,
-               int normalize, float* __restrict__ out, float* __restrict__ sums) {
+               int normalize, float* __restrict__ out, float* __restrict__ sums,
+               const float* __restrict__ shift = nullptr) {
   constexpr int EPS = kWave / H;  // edges per step
   constexpr int NB = H < 8 ? H : 8;
   const int lane = threadIdx.x & (kWave - 1);
@@ -2303,6 +2326,7 @@ k_edge_softmax(const int64_t* __restrict__ indptr, const int32_t* __restrict__ i
   const int h = lane % H, k = lane / H;
   const int64_t beg = indptr[row], end = indptr[row + 1];
   const float ar = a[row * lda + h];
+  const float mr = SH ? shift[row * H + h] : 0.f;
   float s = 0.f;
   for (int pass = 0; pass < 2; ++pass) {
     const float inv = s;  // pass 1: row sum (division below, not a reciprocal)
@@ -2320,7 +2344,7 @@ k_edge_softmax(const int64_t* __restrict__ indptr, const int32_t* __restrict__ i
           }
 #pragma unroll
           for (int j = 0; j < NB; ++j) {
-            const float x = sf_apply(sf, ar + v[j]);
+            const float x = SH ? sf_shift(sf, ar + v[j], mr) : sf_apply(sf, ar + v[j]);
             float* o = out + (e0 + (j0 + j) * EPS + k) * H + h;
             if (pass == 0) {
               s += x;
@@ -2335,7 +2359,8 @@ k_edge_softmax(const int64_t* __restrict__ indptr, const int32_t* __restrict__ i
           const int slot = j * EPS + k;
           const int src = __shfl(mine, slot < cnt ? slot : 0);
           if (slot < cnt) {
-            const float x = sf_apply(sf, ar + b[static_cast<int64_t>(src) * ldb + h]);
+            const float bv = b[static_cast<int64_t>(src) * ldb + h];
+            const float x = SH ? sf_shift(sf, ar + bv, mr) : sf_apply(sf, ar + bv);
             float* o = out + (e0 + slot) * H + h;
             if (pass == 0) {
               s += x;
@@ -2362,21 +2387,23 @@ k_edge_softmax(const int64_t* __restrict__ indptr, const int32_t* __restrict__ i
 // VGPRs; later chunks park v in `out` during pass 1 and pass 2 reads it back
 // (coalesced), so every source row is gathered exactly once.  Row sums: per
 // lane, then a butterfly over all 64 lanes.
-template <int H, int K>
+template <int H, int K, bool SH = false>
 __global__ void __launch_bounds__(kBlock)
 k_edge_softmax_v(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
                  const float* __restrict__ a, int64_t lda, const float* __restrict__ b, int64_t ldb, int sf,
-                 int normalize, float* __restrict__ out, float* __restrict__ sums) {
+                 int normalize, float* __restrict__ out, float* __restrict__ sums,
+                 const float* __restrict__ shift = nullptr) {
   constexpr int Q = H / 4;
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
   if (row >= n_rows) return;
   const int64_t beg = indptr[row], end = indptr[row + 1];
-  float ar[H], s[H];
+  float ar[H], s[H], mr[SH ? H : 1];
 #pragma unroll
   for (int h = 0; h < H; ++h) {
     ar[h] = a[row * lda + h];
     s[h] = 0.f;
+    if (SH) mr[h] = shift[row * H + h];
   }
   float4 keep[K][Q];
   auto visit = [&](int64_t e0, float4 (&v)[Q]) {  // gather + sf for the chunk at e0; returns v in place
@@ -2391,7 +2418,8 @@ k_edge_softmax_v(const int64_t* __restrict__ indptr, const int32_t* __restrict__
       float* c = reinterpret_cast<float*>(&v[q]);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const float x = ok ? sf_apply(sf, ar[4 * q + t] + c[t]) : 0.f;
+        const float sv = ar[4 * q + t] + c[t];
+        const float x = ok ? (SH ? sf_shift(sf, sv, mr[SH ? 4 * q + t : 0]) : sf_apply(sf, sv)) : 0.f;
         c[t] = x;
         s[4 * q + t] += x;
       }
@@ -2455,6 +2483,54 @@ k_edge_softmax_v(const int64_t* __restrict__ indptr, const int32_t* __restrict__
       }
     }
   }
+}
+
+// The shifted softmax's row maxima: shift[row, h] = max over the row's edges of g(a[row, h] +
+// b[src, h]) for sf = exp . g.  fp32 addition and g are monotone non-decreasing in b, so this is
+// g(a[row, h] + max_e b[src(e), h]) bit for bit: a max over b alone, g applied once.  One wave
+// per row, lane = k*H + h as in k_edge_softmax: 64 indices per coalesced load, H consecutive
+// floats of b per edge, gathers issued NB at a time.  red_max propagates NaN (a poisoned guard
+// band must not be swallowed); idle slots hold -inf; a row without edges gets 0, decided from
+// its degree.
+template <int H>
+__global__ void __launch_bounds__(kBlock)
+k_softmax_shift(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
+                const float* __restrict__ a, int64_t lda, const float* __restrict__ b, int64_t ldb, int sf,
+                float* __restrict__ shift) {
+  constexpr int EPS = kWave / H;  // edges per step
+  constexpr int NB = H < 8 ? H : 8;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  if (row >= n_rows) return;
+  const int h = lane % H, k = lane / H;
+  const int64_t beg = indptr[row], end = indptr[row + 1];
+  float m = -INFINITY;
+  for (int64_t e0 = beg; e0 < end; e0 += kWave) {
+    const int cnt = (end - e0 < kWave) ? static_cast<int>(end - e0) : kWave;
+    const int mine = (lane < cnt) ? indices[e0 + lane] : 0;
+    if (cnt == kWave) {
+#pragma unroll
+      for (int j0 = 0; j0 < H; j0 += NB) {
+        float v[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const int src = __shfl(mine, (j0 + j) * EPS + k);
+          v[j] = b[static_cast<int64_t>(src) * ldb + h];
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) m = red_max(m, v[j]);
+      }
+    } else {
+      for (int j = 0; j * EPS < cnt; ++j) {
+        const int slot = j * EPS + k;
+        const int src = __shfl(mine, slot < cnt ? slot : 0);
+        if (slot < cnt) m = red_max(m, b[static_cast<int64_t>(src) * ldb + h]);
+      }
+    }
+  }
+#pragma unroll
+  for (int off = H; off < kWave; off <<= 1) m = red_max(m, __shfl_xor(m, off));
+  if (k == 0) shift[row * H + h] = (end > beg) ? sf_g(sf, a[row * lda + h] + m) : 0.f;
 }
 
 // ---------------------------------------------------------------------------
@@ -4826,31 +4902,37 @@ int64_t gta_gat_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, i
          static_cast<int64_t>(sizeof(float));
 }
 
-int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
-                              int64_t nnz, const float* x, int64_t ldx, int64_t F, const float* a_dst, int64_t lda,
-                              const float* b_src, int64_t ldb, int64_t heads, int sf, int normalize, int sf_out,
-                              float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks, int64_t item_edges,
-                              void* workspace, void* stream) {
+// gta_gat_aggregate_blocked (shifted false) and gta_gat_aggregate_blocked_shifted: one argument check,
+// one dispatch; the unshifted launches are the instantiations they always were.
+static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64_t* indptr, const int32_t* indices,
+                                      int64_t n_rows, int64_t n_cols, int64_t nnz, const float* x, int64_t ldx,
+                                      int64_t F, const float* a_dst, int64_t lda, const float* b_src, int64_t ldb,
+                                      int64_t heads, int sf, int normalize, int sf_out, float* y, int64_t ldy,
+                                      float* sums, const void* plan, int64_t blocks, int64_t item_edges,
+                                      void* workspace, const float* shift, void* stream) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
   if (n_rows < 0 || nnz < 0 || blocks < 1 || blocks > 63 || heads <= 0 || lda < heads || ldb < heads ||
       item_edges < 1 || sf_out < GTA_SF_NONE || sf_out > GTA_SF_RECIP)
-    return fail(GTA_ERR_ARG, "gat_aggregate_blocked: bad sizes");
+    return fail(GTA_ERR_ARG, std::string(who) + ": bad sizes");
+  if (shifted && !shift) return fail(GTA_ERR_ARG, std::string(who) + ": shift is required");
+  if (shifted && !sf_is_exp_form(sf))
+    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": sf must be EXP_LEAKY_RELU or EXP");
   if (n_rows == 0) return GTA_OK;
   if (!indptr || !x || !a_dst || !b_src || !y || !plan || (!workspace && nnz > 0))
-    return fail(GTA_ERR_ARG, "gat_aggregate_blocked: bad arguments");
+    return fail(GTA_ERR_ARG, std::string(who) + ": bad arguments");
   const int vq = static_cast<int>(F / 16);
   if ((F != 64 && F != 128 && F != 256) || F % heads || (F / heads) % vq || ldx % 4 || !aligned(x, 16) ||
       ldy % (F / 64) || !aligned(y, 4 * (F / 64)))
-    return fail(GTA_ERR_UNSUPPORTED, "gat_aggregate_blocked: F in {64,128,256}, 16-B rows, F/heads a multiple of F/16");
+    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": F in {64,128,256}, 16-B rows, F/heads a multiple of F/16");
   const int lph = static_cast<int>((F / heads) / vq);
-  if (lph < 1 || 16 % lph) return fail(GTA_ERR_UNSUPPORTED, "gat_aggregate_blocked: lanes per head must divide 16");
+  if (lph < 1 || 16 % lph) return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": lanes per head must divide 16");
   const int B = static_cast<int>(blocks);
   const int64_t mi = blocked_max_items(n_rows, nnz, B, item_edges);
   BlockedView v = blocked_view(const_cast<void*>(plan), n_rows, B, mi);
   const RowItems ri{v.row_ptr, v.row_items};
   hipStream_t s = S(stream);
   float* slabs = static_cast<float*>(workspace);
-  AttArgs att{a_dst, lda, b_src, ldb, sf, static_cast<int>(heads)};
+  AttArgs att{a_dst, lda, b_src, ldb, sf, static_cast<int>(heads), shift};
   const int64_t items = mi;
   const int64_t* nit = &v.hdr[4];
   const dim3 g4(static_cast<unsigned>((items + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock))), blk(kBlock);
@@ -4859,7 +4941,11 @@ int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int
   if (items > 0) {  // no edges: no items, the reduce alone writes the empty rows
   const bool elr = sf == GTA_SF_EXP_LEAKY_RELU;  // GAT's score function, specialised
 #define GTA_ATT(VW_, U_)                                                                                          \
-  if (elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU><<<g4, blk, 0, s>>>(                        \
+  if (shifted && elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 16, true><<<g4, blk, 0, s>>>(   \
+      indices, nit, x, ldx, nullptr, 0, lph, slabs, it, att);                                            \
+  else if (shifted) k_agg_seg4<VW_, U_, false, 0, true, -1, 16, true><<<g4, blk, 0, s>>>(                        \
+      indices, nit, x, ldx, nullptr, 0, lph, slabs, it, att);                                            \
+  else if (elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU><<<g4, blk, 0, s>>>(                   \
       indices, nit, x, ldx, nullptr, 0, lph, slabs, it, att);                                            \
   else k_agg_seg4<VW_, U_, false, 0, true><<<g4, blk, 0, s>>>(indices, nit, x, ldx, nullptr, 0, lph, slabs, \
                                                              it, att)
@@ -4875,11 +4961,19 @@ int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int
     const bool direct = (tuning().att_direct == 2 || (tuning().att_direct == 1 && B <= 2)) && ldy % 4 == 0 && aligned(y, 16);
     skip_single = direct;
     const int64_t* rp = direct ? v.row_ptr : nullptr;
-    k_att_h32<2><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp, normalize, y,
-                                     ldy, sums, sf_out);  // NT bit 2: non-temporal slab stores
+    if (shifted)
+      k_att_h32<2, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp, normalize,
+                                             y, ldy, sums, sf_out, shift);
+    else
+      k_att_h32<2><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp, normalize, y,
+                                       ldy, sums, sf_out);  // NT bit 2: non-temporal slab stores
   } else if (F == 128 && (F / heads) % 4 == 0 && lph32 >= 1 && 32 % lph32 == 0) {
     const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
-    if (elr) k_agg_seg4<4, 8, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 32><<<g2h, blk, 0, s>>>(
+    if (shifted && elr) k_agg_seg4<4, 8, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 32, true><<<g2h, blk, 0, s>>>(
+        indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
+    else if (shifted) k_agg_seg4<4, 8, false, 0, true, -1, 32, true><<<g2h, blk, 0, s>>>(
+        indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
+    else if (elr) k_agg_seg4<4, 8, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 32><<<g2h, blk, 0, s>>>(
         indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
     else k_agg_seg4<4, 8, false, 0, true, -1, 32><<<g2h, blk, 0, s>>>(indices, nit, x, ldx, nullptr, 0,
                                                                       lph32, slabs, it, att);
@@ -4895,6 +4989,27 @@ int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int
   else k_seg_reduce_att<4><<<g3, blk, 0, s>>>(n_rows, slabs, H, normalize, y, ldy, sums, ri, 0, sf_out);
   GTA_LAUNCHED("k_seg_reduce_att");
   return GTA_OK;
+}
+
+int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                              int64_t nnz, const float* x, int64_t ldx, int64_t F, const float* a_dst, int64_t lda,
+                              const float* b_src, int64_t ldb, int64_t heads, int sf, int normalize, int sf_out,
+                              float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks, int64_t item_edges,
+                              void* workspace, void* stream) {
+  return gat_aggregate_blocked_impl("gat_aggregate_blocked", false, indptr, indices, n_rows, n_cols, nnz, x, ldx, F,
+                                    a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums, plan, blocks,
+                                    item_edges, workspace, nullptr, stream);
+}
+
+int gta_gat_aggregate_blocked_shifted(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                                      int64_t nnz, const float* x, int64_t ldx, int64_t F, const float* a_dst,
+                                      int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf,
+                                      int normalize, int sf_out, float* y, int64_t ldy, float* sums, const void* plan,
+                                      int64_t blocks, int64_t item_edges, void* workspace, const float* shift,
+                                      void* stream) {
+  return gat_aggregate_blocked_impl("gat_aggregate_blocked_shifted", true, indptr, indices, n_rows, n_cols, nnz, x,
+                                    ldx, F, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums, plan,
+                                    blocks, item_edges, workspace, shift, stream);
 }
 
 }  // extern "C"
@@ -5261,25 +5376,35 @@ int gta_apply_node(int bin, int sf, int64_t n, const void* a, int64_t lda, int64
   return GTA_OK;
 }
 
-int gta_edge_softmax(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
-                     const float* a_dst, int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf,
-                     int normalize, float* out, float* sums, void* stream) {
+// gta_edge_softmax (shift NULL, shifted false) and gta_edge_softmax_shifted: one argument check, one
+// dispatch; the unshifted launches are the instantiations they always were.
+static int edge_softmax_impl(const char* who, bool shifted, const int64_t* indptr, const int32_t* indices,
+                             int64_t n_rows, int64_t nnz, const float* a_dst, int64_t lda, const float* b_src,
+                             int64_t ldb, int64_t heads, int sf, int normalize, float* out, float* sums,
+                             const float* shift, void* stream) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
-  if (!indptr || !a_dst || !b_src || n_rows < 0 || nnz < 0 || (nnz > 0 && (!indices || !out)))
-    return fail(GTA_ERR_ARG, "edge_softmax: bad arguments");
+  if (!indptr || !a_dst || !b_src || n_rows < 0 || nnz < 0 || (nnz > 0 && (!indices || !out)) || (shifted && !shift))
+    return fail(GTA_ERR_ARG, std::string(who) + ": bad arguments");
   if (heads <= 0 || heads > kWave || (heads & (heads - 1)))
-    return fail(GTA_ERR_UNSUPPORTED, "edge_softmax: heads must be a power of two <= 64");
-  if (lda < heads || ldb < heads) return fail(GTA_ERR_ARG, "edge_softmax: leading dimension < heads");
+    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": heads must be a power of two <= 64");
+  if (shifted && !sf_is_exp_form(sf))
+    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": sf must be EXP_LEAKY_RELU or EXP");
+  if (lda < heads || ldb < heads) return fail(GTA_ERR_ARG, std::string(who) + ": leading dimension < heads");
   if (n_rows == 0) return GTA_OK;
   const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
   const bool vec = tuning().esm_lane && (heads == 4 || heads == 8 || heads == 16) && ldb % 4 == 0 && aligned(b_src, 16) &&
                    (nnz == 0 || aligned(out, 16));
   if (vec) {
 #define GTA_ESMV(H_, K_)                                                                                          \
-  k_edge_softmax_v<H_, K_><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src, ldb, \
-                                                                 sf, normalize, out, sums)
+  if (shifted)                                                                                                    \
+    k_edge_softmax_v<H_, K_, true><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda,     \
+                                                                         b_src, ldb, sf, normalize, out, sums,    \
+                                                                         shift);                                  \
+  else                                                                                                            \
+    k_edge_softmax_v<H_, K_><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src,    \
+                                                                   ldb, sf, normalize, out, sums)
     // chunks of 64 edges held in VGPRs: 4 for H <= 8, 2 at H = 16 (register budget)
-    if (heads == 4) GTA_ESMV(4, 4); else if (heads == 8) GTA_ESMV(8, 4); else GTA_ESMV(16, 2);
+    if (heads == 4) { GTA_ESMV(4, 4); } else if (heads == 8) { GTA_ESMV(8, 4); } else { GTA_ESMV(16, 2); }
 #undef GTA_ESMV
     GTA_LAUNCHED("k_edge_softmax_v");
     return GTA_OK;
@@ -5287,13 +5412,57 @@ int gta_edge_softmax(const int64_t* indptr, const int32_t* indices, int64_t n_ro
   switch (heads) {
 #define GTA_ESM(H_)                                                                                         \
   case H_:                                                                                                  \
-    k_edge_softmax<H_><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src, ldb, \
-                                                             sf, normalize, out, sums);                       \
+    if (shifted)                                                                                            \
+      k_edge_softmax<H_, true><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda,   \
+                                                                     b_src, ldb, sf, normalize, out, sums,  \
+                                                                     shift);                                \
+    else                                                                                                    \
+      k_edge_softmax<H_><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src,  \
+                                                               ldb, sf, normalize, out, sums);              \
     break;
     GTA_ESM(1) GTA_ESM(2) GTA_ESM(4) GTA_ESM(8) GTA_ESM(16) GTA_ESM(32) GTA_ESM(64)
 #undef GTA_ESM
   }
   GTA_LAUNCHED("k_edge_softmax");
+  return GTA_OK;
+}
+
+int gta_edge_softmax(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
+                     const float* a_dst, int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf,
+                     int normalize, float* out, float* sums, void* stream) {
+  return edge_softmax_impl("edge_softmax", false, indptr, indices, n_rows, nnz, a_dst, lda, b_src, ldb, heads, sf,
+                           normalize, out, sums, nullptr, stream);
+}
+
+int gta_edge_softmax_shifted(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
+                             const float* a_dst, int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf,
+                             int normalize, float* out, float* sums, const float* shift, void* stream) {
+  return edge_softmax_impl("edge_softmax_shifted", true, indptr, indices, n_rows, nnz, a_dst, lda, b_src, ldb, heads,
+                           sf, normalize, out, sums, shift, stream);
+}
+
+int gta_softmax_shift(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const float* a_dst,
+                      int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf, float* shift,
+                      void* stream) {
+  if (!indptr || !a_dst || !shift || n_rows < 0 || nnz < 0 || (nnz > 0 && (!indices || !b_src)))
+    return fail(GTA_ERR_ARG, "softmax_shift: bad arguments");
+  if (heads <= 0 || heads > kWave || (heads & (heads - 1)))
+    return fail(GTA_ERR_UNSUPPORTED, "softmax_shift: heads must be a power of two <= 64");
+  if (!sf_is_exp_form(sf)) return fail(GTA_ERR_UNSUPPORTED, "softmax_shift: sf must be EXP_LEAKY_RELU or EXP");
+  if (lda < heads || ldb < heads) return fail(GTA_ERR_ARG, "softmax_shift: leading dimension < heads");
+  if (n_rows == 0) return GTA_OK;
+  // nnz == 0: every degree is 0, the kernel writes zeros and reads neither indices nor b_src
+  const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
+  switch (heads) {
+#define GTA_SSH(H_)                                                                                          \
+  case H_:                                                                                                   \
+    k_softmax_shift<H_><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src, ldb, \
+                                                              sf, shift);                                    \
+    break;
+    GTA_SSH(1) GTA_SSH(2) GTA_SSH(4) GTA_SSH(8) GTA_SSH(16) GTA_SSH(32) GTA_SSH(64)
+#undef GTA_SSH
+  }
+  GTA_LAUNCHED("k_softmax_shift");
   return GTA_OK;
 }
 

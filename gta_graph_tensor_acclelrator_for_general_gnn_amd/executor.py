@@ -159,13 +159,20 @@ def _mean_scale(g):
     return s
 
 
+# Executor.softmax_shift's default.  True: a matched softmax chain whose SF is an exp-form (SHIFT_SFS) subtracts
+# its row maximum before the exp (ops.softmax_shift once per chain, then the shifted edge_softmax /
+# gat_aggregate_blocked): no overflow to inf / inf, no 0 / 0 for trained attention scores.  False: the unshifted kernels.
+SOFTMAX_SHIFT = False
+SHIFT_SFS = ("EXP_LEAKY_RELU", "EXP")
+
 EDGE_EXPR = True  # Executor.edge_expr's default (gta_aggregate_expr for applyedge trees); False: unfused (A/B)
 
 MAX_MATERIALIZE_BYTES = 96 << 30  # refuse to materialise a single edge tensor larger than this
 
 
 class Executor:
-    def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, dist=None):
+    def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, dist=None,
+                 softmax_shift=None):
         self.g = opgraph
         # dist (distributed.Comm): node tensors are this rank's row block; gathers are
         # reduce-scattered to it and dst-side scatters all-gather it (distributed.py)
@@ -213,6 +220,10 @@ class Executor:
         self.attention_blocks = None
         self.attn = self._match_attention()
         self._att_state = {}
+        #   softmax_shift: the chains' exp-form SFs run overflow-safe (SOFTMAX_SHIFT above); the row-max
+        #   table of a chain is built once, on first use, and handed to both of its launches
+        self.softmax_shift = SOFTMAX_SHIFT if softmax_shift is None else bool(softmax_shift)
+        self._att_shift = {}  # score op A -> Lazy shift table [n, H] (beside _att_state)
         #   mm_first: a gather whose only consumer is a narrowing applynode MM is executed as
         #   MM-then-aggregate (sum_e w_e x_src) W == sum_e w_e (x W)_src -- the layer's output
         #   to fp32 rounding, the gather's own value computed only if something asks for it
@@ -847,6 +858,7 @@ class Executor:
         if st is None or not isinstance(sv, Scat) or sv.mode != "src":
             return None
         a, b, sf = st
+        shift = self._att_shift.get(pat["A"])
         x = sv.t
         F, H = x.shape[1], a.shape[1]
         if x.dtype != torch.float32 or not ops.BlockedPlan.supports_att(F, H):
@@ -861,10 +873,15 @@ class Executor:
         G = pat["G"]
         gv = self.values.get(G)
         want = not norm and isinstance(gv, Lazy) and gv.v is None
-        y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
-                                            sf_out=sf_out)
         E, n = self.graph.nnz, self.graph.n_rows
-        self._count(E * (4 + 4 * F + 4 * H) + n * (8 + 4 * F + 4 * H))
+        if shift is not None:
+            y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
+                                                sf_out=sf_out, shift=shift.force())
+            self._count(E * (4 + 4 * F + 4 * H) + n * (8 + 4 * F + 8 * H))
+        else:
+            y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
+                                                sf_out=sf_out)
+            self._count(E * (4 + 4 * F + 4 * H) + n * (8 + 4 * F + 4 * H))
         if want:
             self.values[G] = NodeT(sums)
         return NodeT(y)
@@ -882,8 +899,20 @@ class Executor:
         V, sf, norm = self.g.ops[pat["V"]], self.sem.sf_of(self.g.ops[pat["V"]]), pat["D"] is not None
         E, n = self.graph.nnz, self.graph.n_rows
         self._att_state[A.idx] = (a, b, sf)
+        shift = None
+        if self.softmax_shift and sf in SHIFT_SFS:
+            def build_shift():  # one pass over the indices and b; a and the table per row
+                t = ops.softmax_shift(self.graph, a, b, sf)
+                self._count(E * (4 + 4 * H) + n * (8 + 8 * H))
+                return t
+            shift = self._att_shift[A.idx] = Lazy(build_shift)
 
         def launch():
+            if shift is not None:
+                out, sums = ops.edge_softmax(self.graph, a, b, sf, normalize=norm, want_sums=True,
+                                             shift=shift.force())
+                self._count(E * (4 + 8 * H) + n * (8 + 12 * H))
+                return out, sums
             out, sums = ops.edge_softmax(self.graph, a, b, sf, normalize=norm, want_sums=True)
             self._count(E * (4 + 8 * H) + n * (8 + 8 * H))
             return out, sums
@@ -1294,6 +1323,10 @@ class Executor:
             if op.idx in block.stored and not (self.elide_scatter_stores and self.consumers[op.idx]):
                 return EdgeT(self._to_edge_tensor(s))
             return s
+        if self.softmax_shift and not self.fuse_softmax and op.idx in self.softmax \
+                and self.sem.sf_of(self.g.ops[self.softmax[op.idx]["V"]]) in SHIFT_SFS:
+            raise NotImplementedError(
+                f"op {op.idx}: softmax_shift on column shards (a row's maximum spans ranks); row-local shards work")
         if self.fuse_softmax and op.idx in self.softmax:
             v = self._eval_softmax(op, self.softmax[op.idx])
             if v is not None:
@@ -1626,12 +1659,13 @@ def set_auto_graph(flag):
         clear_auto_graphs()
 
 
-def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk):
+def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=None):
     """-> a GraphedRun to replay for this call, or None (run eagerly)."""
     if ops.Tuning.attached(torch.cuda.current_stream(graph.device)):
         return None  # a knob set on this stream: every call reads it (gta.h), so no cached graph
     refs = (opgraph, stream, graph, semantics)
-    fkey = (id(opgraph), id(stream), id(graph), id(semantics), plan_chunk, id(tensors), ops.knob_state())
+    shifted = SOFTMAX_SHIFT if softmax_shift is None else bool(softmax_shift)
+    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted), id(tensors), ops.knob_state())
     ent = _AUTO_FAST.get(fkey)
     if ent is not None and not (ent.src is tensors and all(a is b for a, b in zip(ent.refs, refs)) and
                                 len(tensors) == len(ent.tensors) and
@@ -1664,7 +1698,8 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk):
     if ent.run is None:
         before = torch.cuda.memory_reserved(graph.device)
         try:
-            ent.run = GraphedRun(opgraph, stream, graph, ent.tensors, semantics, plan_chunk, warmup=1)
+            ent.run = GraphedRun(opgraph, stream, graph, ent.tensors, semantics, plan_chunk, warmup=1,
+                                 softmax_shift=shifted)
         except Exception:  # something in this stream is not capturable: stay eager for this key
             ent.failed = True
             torch.cuda.synchronize(graph.device)
@@ -1692,12 +1727,14 @@ def _evict_pools(keep):
         e.run, e.evicted = None, True
 
 
-def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, sync=True, trace=False):
+def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, sync=True, trace=False,
+               softmax_shift=None):
+    """softmax_shift: Executor.softmax_shift for this call (None: the module's SOFTMAX_SHIFT)."""
     dev = graph.device
     if not AUTO_GRAPH and _AUTO:
         clear_auto_graphs()
     if AUTO_GRAPH and not trace and dev.type == "cuda" and graph.nnz <= AUTO_GRAPH_MAX_EDGES:
-        gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk)
+        gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift)
         if gr is not None:
             if sync:
                 torch.cuda.synchronize(dev)
@@ -1707,7 +1744,7 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
                 torch.cuda.synchronize(dev)
             ex = gr.executor
             return ExecResult(ex.values, outputs, time.perf_counter() - t0, ex.alg_bytes, ex.launches), ex
-    ex = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk)
+    ex = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift)
     ex.trace = trace
     sync = sync and dev.type == "cuda"
     if sync:
@@ -1894,7 +1931,8 @@ class GraphedRun:
     the W^T tensors (and sibling-weight concatenations) it reads alive, and a weight changed in
     place (its version moved) is re-concatenated / re-transposed into them before the next replay."""
 
-    def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, warmup=2):
+    def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, warmup=2,
+                 softmax_shift=None):
         if graph.device.type != "cuda":
             raise RuntimeError("GraphedRun captures device launches: the graph must be on a HIP device")
         self.tensors = tensors
@@ -1902,7 +1940,7 @@ class GraphedRun:
         side.wait_stream(torch.cuda.current_stream(graph.device))
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
-                Executor(opgraph, stream, graph, tensors, semantics, plan_chunk).run()
+                Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift).run()
         torch.cuda.current_stream(graph.device).wait_stream(side)
         torch.cuda.synchronize(graph.device)
         self.cuda_graph = torch.cuda.CUDAGraph()
@@ -1910,7 +1948,8 @@ class GraphedRun:
         del _CAPTURED_WCAT[:]
         try:
             with torch.cuda.graph(self.cuda_graph):
-                self.executor = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk)
+                self.executor = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk,
+                                         softmax_shift=softmax_shift)
                 self.outputs = self.executor.run()
         finally:
             taken, ops._CAPTURED_WT[:] = list(ops._CAPTURED_WT), []

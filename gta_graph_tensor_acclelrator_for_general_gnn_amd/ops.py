@@ -455,13 +455,21 @@ def blocked_ready(graph, blocks):
     return graph.blocked_plan(blocks).sorted
 
 
+def _shift_table(graph, shift, H, who):
+    if shift.dtype != torch.float32 or not shift.is_contiguous() or tuple(shift.shape) != (graph.n_rows, H):
+        raise ValueError(f"{who}: shift must be a contiguous float32 [N, heads] tensor (ops.softmax_shift)")
+    return shift
+
+
 def gat_aggregate_blocked(graph, x, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize=True, out=None, sums=None,
-                          want_sums=False, plan=None, blocks=16, sf_out=None):
+                          want_sums=False, plan=None, blocks=16, sf_out=None, shift=None):
     """Fused GAT attention aggregate (gta_gat_aggregate_blocked): with v = sf(a_dst[dst] + b_src[src]),
     normalize: out[i] = sum_e v x[src] / sum_e v per head (GAT ops 6-12); else the numerator alone.
     sf_out: an SF applied to out as it is written (GAT op 13; None = none), bitwise equal to
-    apply_node(None, sf_out, out).  sums[i, h] = sum_e v (want_sums / sums given).  Returns (out, sums)."""
-    _need_gpu(x, a_dst, b_src, out, sums, graph.indptr)
+    apply_node(None, sf_out, out).  sums[i, h] = sum_e v (want_sums / sums given).  Returns (out, sums).
+    shift: None, or the row-max table of softmax_shift for the same graph, scores and sf: the
+    overflow-safe form (gta_gat_aggregate_blocked_shifted), v = exp(g(a + b) - shift[dst])."""
+    _need_gpu(x, a_dst, b_src, out, sums, shift, graph.indptr)
     F, H = x.shape[1], a_dst.shape[1]
     if b_src.shape[1] != H:
         raise ValueError("gat_aggregate_blocked: a_dst and b_src need the same head count")
@@ -480,6 +488,14 @@ def gat_aggregate_blocked(graph, x, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize
     if sums is not None and (not sums.is_contiguous() or tuple(sums.shape) != (graph.n_rows, H)):
         raise ValueError("gat_aggregate_blocked: sums must be a contiguous [N, heads] tensor")
     ws = plan.workspace_att(F, H)
+    if shift is not None:
+        _shift_table(graph, shift, H, "gat_aggregate_blocked")
+        check(_L().gta_gat_aggregate_blocked_shifted(
+            _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols, graph.nnz, _ptr(x), _rows(x, "x"), F,
+            _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"), H, _sf(sf), 1 if normalize else 0,
+            _sf(sf_out), _ptr(out), _rows(out, "out"), _ptr(sums), _ptr(plan.buf), plan.blocks, plan.item_edges,
+            _ptr(ws), _ptr(shift), _stream(x.device)), "gat_aggregate_blocked_shifted")
+        return out, sums
     check(_L().gta_gat_aggregate_blocked(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols,
                                          graph.nnz, _ptr(x), _rows(x, "x"), F, _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src),
                                          _rows(b_src, "b_src"), H, _sf(sf), 1 if normalize else 0, _sf(sf_out), _ptr(out),
@@ -643,12 +659,34 @@ def _flat_aligned(Fo, a, lda, b, ldb, out, ldo):
     return ok(a, lda, a.shape[1]) and ok(b, ldb, None if b is None else b.shape[1]) and ok(out, ldo, Fo)
 
 
+def softmax_shift(graph, a_dst, b_src, sf="EXP_LEAKY_RELU", out=None):
+    """The shifted softmax's row maxima (gta_softmax_shift): for sf = exp . g ("EXP_LEAKY_RELU" or
+    "EXP"), out[i, h] = max over row i's edges of g(a_dst[i, h] + b_src[src(e), h]), rows without
+    edges 0; NaN propagates.  Returns the float32 [N, H] table that edge_softmax(..., shift=) and
+    gat_aggregate_blocked(..., shift=) subtract before the exp."""
+    _need_gpu(a_dst, b_src, out, graph.indptr)
+    H = a_dst.shape[1]
+    if b_src.shape[1] != H:
+        raise ValueError("softmax_shift: a_dst and b_src need the same head count")
+    if a_dst.shape[0] < graph.n_rows or b_src.shape[0] < graph.n_cols:
+        raise ValueError("softmax_shift: score tensors have too few rows")
+    if out is None:
+        out = torch.empty(graph.n_rows, H, dtype=torch.float32, device=a_dst.device)
+    _shift_table(graph, out, H, "softmax_shift")
+    check(_L().gta_softmax_shift(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz, _ptr(a_dst),
+                                 _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"), H, _sf(sf), _ptr(out),
+                                 _stream(a_dst.device)), "softmax_shift")
+    return out
+
+
 def edge_softmax(graph, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize=True, out=None, sums=None,
-                 want_sums=False):
+                 want_sums=False, shift=None):
     """Fused GAT edge-softmax (GAT ops 6-10, vTCAD/GraphOP/genGraphOP.py:51-60):
     v[e] = sf(a_dst[dst(e)] + b_src[src(e)]); sums[i] = sum_{e in row i} v[e];
-    out[e] = v[e] / sums[dst(e)] (normalize) or v[e].  Returns (out [E, H], sums [N, H] or None)."""
-    _need_gpu(a_dst, b_src, out, sums, graph.indptr)
+    out[e] = v[e] / sums[dst(e)] (normalize) or v[e].  Returns (out [E, H], sums [N, H] or None).
+    shift: None, or the row-max table of softmax_shift for the same graph, scores and sf: the
+    overflow-safe form (gta_edge_softmax_shifted), v[e] = exp(g(a + b) - shift[dst(e)]) <= 1."""
+    _need_gpu(a_dst, b_src, out, sums, shift, graph.indptr)
     H = a_dst.shape[1]
     if b_src.shape[1] != H:
         raise ValueError("edge_softmax: a_dst and b_src need the same head count")
@@ -662,6 +700,13 @@ def edge_softmax(graph, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize=True, out=N
         sums = torch.empty(graph.n_rows, H, dtype=torch.float32, device=a_dst.device)
     if sums is not None and (not sums.is_contiguous() or tuple(sums.shape) != (graph.n_rows, H)):
         raise ValueError("edge_softmax: sums must be a contiguous [N, H] tensor")
+    if shift is not None:
+        _shift_table(graph, shift, H, "edge_softmax")
+        check(_L().gta_edge_softmax_shifted(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz,
+                                            _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"), H,
+                                            _sf(sf), 1 if normalize else 0, _ptr(out), _ptr(sums), _ptr(shift),
+                                            _stream(a_dst.device)), "edge_softmax_shifted")
+        return out, sums
     check(_L().gta_edge_softmax(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz, _ptr(a_dst),
                                 _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"), H, _sf(sf),
                                 1 if normalize else 0, _ptr(out), _ptr(sums), _stream(a_dst.device)),

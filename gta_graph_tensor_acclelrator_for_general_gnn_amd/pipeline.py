@@ -16,13 +16,17 @@ class Layer:
     """One compiled GNN layer bound to a graph: op graph, chosen partition, stream."""
 
     def __init__(self, network, layer, graph, feature, reorder=False, heads=16, candidate=0, tile_start=None,
-                 op_array=None, tile_size_list=None, metadata=None, pingpang=True, sinput=False, aggregator="ADD"):
+                 op_array=None, tile_size_list=None, metadata=None, pingpang=True, sinput=False, aggregator="ADD",
+                 stable_softmax=False):
         """pingpang / sinput: compile()'s isPingpang / isSinput (code/compiler.py:475-510) for the
         fusion search; the reference's start.py passes its command-line flags through.
         aggregator: the message gathers' reduce function, "ADD" / "MAX" / "MIN" / "MEAN"
-        (frontend.gen_ops; the gathers' COMP_TYPE, executed by gta_reduce / the scaled aggregate)."""
+        (frontend.gen_ops; the gathers' COMP_TYPE, executed by gta_reduce / the scaled aggregate).
+        stable_softmax: run() evaluates the layer's softmax chains overflow-safe, exp(s - row max)
+        (Executor.softmax_shift); off, the default, is the unshifted path."""
         self.network, self.layer, self.reorder = network, layer, reorder
         self.aggregator = aggregator
+        self.stable_softmax = bool(stable_softmax)
         self.graph = graph
         self.records = frontend.gen_ops(network, layer, graph.n_rows, graph.nnz, feature, reorder, heads, aggregator)
         self.sem = Semantics.for_network(network, reorder)
@@ -70,7 +74,11 @@ class Layer:
     def run(self, tensors, plan_chunk=512, model=None, sync=True):
         """sync=False: no device synchronisation around the stream (res.elapsed_s is then host time
         only); a multi-layer forward synchronises once at its end instead of twice per layer."""
-        res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync)
+        if self.stable_softmax:
+            res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync,
+                                          softmax_shift=True)
+        else:
+            res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync)
         if model:
             executor.attach_model(res, self.stream_records, self.tile_size_list, self.graph, model)
         return res, ex

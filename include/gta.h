@@ -49,7 +49,9 @@ extern "C" {
                               gta_aggregate_self, bf16 x of gta_update_mlp; 11: gta_gather_add takes the ISA
                               DIRECTION (dir R / C) and the CSC view of gta_csc_build; 12:
                               gta_build_id, gta_synth_alpha and gta_row_ids (scan-free setup); 13: gta_apply_edge_flat;
-                              14: gta_aggregate_expr; 15: gta_reduce (gather MAX / MIN) */
+                              14: gta_aggregate_expr; 15: gta_reduce (gather MAX / MIN);
+                              15 (additive): shifted softmax (gta_softmax_shift, gta_edge_softmax_shifted,
+                              gta_gat_aggregate_blocked_shifted; no existing signature changes) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -311,6 +313,45 @@ int gta_gather_add(int dir, const int64_t* indptr, int64_t n_rows, int64_t nnz, 
 int gta_edge_softmax(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
                      const float* a_dst, int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf,
                      int normalize, float* out, float* sums, void* stream);
+
+/* ---- Shifted (overflow-safe) softmax, ABI 15 additive ----------------------
+ * gta_edge_softmax and gta_gat_aggregate_blocked evaluate v = exp(g(a + b)) as it stands: a score
+ * above 88.7 gives inf / inf = NaN, a row whose every score is below about -435 gives 0 / 0.  The
+ * shifted twins subtract the row maximum first.  Supported score functions are the exp-forms
+ * sf = exp . g:  GTA_SF_EXP_LEAKY_RELU, g(t) = t > 0 ? t : 0.2f * t;  GTA_SF_EXP, g(t) = t.
+ * Any other sf on these three entry points returns GTA_ERR_UNSUPPORTED.
+ *   score   s(e, h)     = g( fl32( a_dst[dst(e), h] + b_src[src(e), h] ) ): exactly the value the
+ *                         unshifted kernels hand to expf.
+ *   shift   shift[i, h] = max over the edges e of row i of s(e, h); rows without edges get 0.0f.
+ *                         fp32 addition and g are monotone non-decreasing in b, so this equals
+ *                         g( fl32( a_dst[i, h] + max_e b_src[src(e), h] ) ) bit for bit (up to the
+ *                         sign of a zero).  NaN propagates (the compare-select of gta_reduce's MAX,
+ *                         never fmaxf).  Infinite scores: unspecified, may be NaN.
+ *   weight  v(e, h)     = expf( s(e, h) - shift[dst(e), h] ): one fp32 subtraction, then expf.
+ *                         Every v <= 1 and at least one edge of each non-empty row has v == 1.0f,
+ *                         so every row sum is >= 1: no shifted call produces inf, 0 / 0, or a NaN
+ *                         that is not already in its inputs.
+ *   outputs sums[i, h] = sum_e v = the unshifted sum times exp(-shift[i, h]); alpha (normalize) and
+ *                         the normalized y are mathematically unchanged.  With normalize = 0 the
+ *                         numerator (out / y) and the denominator (sums) carry the same per-row
+ *                         factor, which cancels when the layer divides them.
+ * gta_softmax_shift writes shift [n_rows, heads] contiguous (heads in {1,2,4,...,64}); with nnz == 0
+ * it writes zeros and reads neither indices nor b_src.  The two consumers take the arguments of
+ * their unshifted twins (same heads, alignment, plan and workspace rules; the workspace size
+ * functions are shared) plus the required table `shift` (NULL: GTA_ERR_ARG), which must be the one
+ * gta_softmax_shift builds from the same graph, a_dst, b_src and sf. */
+int gta_softmax_shift(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
+                      const float* a_dst, int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf,
+                      float* shift, void* stream);
+int gta_edge_softmax_shifted(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
+                             const float* a_dst, int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf,
+                             int normalize, float* out, float* sums, const float* shift, void* stream);
+int gta_gat_aggregate_blocked_shifted(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                                      int64_t nnz, const float* x, int64_t ldx, int64_t F, const float* a_dst,
+                                      int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf,
+                                      int normalize, int sf_out, float* y, int64_t ldy, float* sums, const void* plan,
+                                      int64_t blocks, int64_t item_edges, void* workspace, const float* shift,
+                                      void* stream);
 
 /* ---- K3 APPLYEDGE element-wise -----------------------------------------
  * out[e, c] = sf( a[ia(e), c_a] (bin) b[ib(e), c_b] )   for c < max(Fa, Fb)

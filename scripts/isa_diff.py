@@ -7,6 +7,7 @@ import collections
 import glob
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -40,8 +41,35 @@ def kernels(so_path, names, arch="gfx950"):
             if not names or any(n in f for n in names)}
 
 
+def demangle(symbols):
+    """{symbol: 'name<template arguments>'} (the parameter list dropped); {} without a demangler."""
+    symbols = list(symbols)
+    cxxfilt = next((c for c in (os.path.join(os.path.dirname(asmcheck.objdump()), "llvm-cxxfilt"),
+                                shutil.which("llvm-cxxfilt"), shutil.which("c++filt")) if c and os.path.exists(c)), None)
+    if cxxfilt is None or not symbols:
+        return {}
+    out = subprocess.run([cxxfilt], input="\n".join(symbols), check=True, capture_output=True, text=True).stdout
+    return {f: d.partition(">(")[0] for f, d in zip(symbols, out.splitlines())}
+
+
+def pair_defaulted(old, new):
+    """A kernel template that gained a trailing parameter defaulted to false (and perhaps an argument
+    that instantiation never reads) changes its symbol: NEW's k<..., false> is OLD's k<...>.  Renames
+    such NEW entries to OLD's symbol so the two are compared; returns how many were paired."""
+    by_name = {d: f for f, d in demangle(old.keys() - new.keys()).items()}
+    n = 0
+    for f, d in demangle(new.keys() - old.keys()).items():
+        if d.endswith(", false") and d[:-len(", false")] in by_name:
+            new[by_name[d[:-len(", false")]]] = new.pop(f)
+            n += 1
+    return n
+
+
 def main(argv):
     old, new = kernels(argv[1], argv[3:]), kernels(argv[2], argv[3:])
+    paired = pair_defaulted(old, new)
+    if paired:
+        print(f"{paired} kernels of NEW paired with OLD's symbol (a trailing template parameter defaulted to false)")
     for f in sorted(old.keys() ^ new.keys()):
         print("only in OLD" if f in old else "only in NEW", f)
     differ = 0

@@ -76,7 +76,9 @@ def main(names=None, reps=5, trace=False, graphed=False):
 if __name__ == "__main__":
     from gta_graph_tensor_acclelrator_for_general_gnn_amd import ops
     argv = [a for a in sys.argv[1:] if a not in ("--trace", "--hipgraph", "--no-mlp", "--graph-all", "--no-bf16-sum",
-                                                 "--no-edge-flat", "--no-edge-expr")]
+                                                 "--no-edge-flat", "--no-edge-expr", "--stable-softmax")]
+    if "--stable-softmax" in sys.argv[1:]:  # the GAT softmax chains shifted by their row maxima (A/B of the shift pass)
+        executor.SOFTMAX_SHIFT = True
     if "--no-edge-expr" in sys.argv[1:]:  # the applyedge trees of DGN / PNA unfused (A/B of gta_aggregate_expr, ABI 14)
         executor.EDGE_EXPR = False
     if "--no-edge-flat" in sys.argv[1:]:  # apply_edge on the row-sweep forms (A/B of gta_apply_edge_flat, ABI 13)
