@@ -49,14 +49,19 @@ __host__ __device__ inline bool aligned(const void* p, int bytes) { return (rein
 // ---------------------------------------------------------------------------
 // special functions (SF post-ops) and binary ops
 // ---------------------------------------------------------------------------
+// Special values: gta.h, "Special values of the SFs".  NaN in gives NaN out of every SF.
 __device__ __forceinline__ float sf_apply(int sf, float v) {
   switch (sf) {
     case GTA_SF_NONE: return v;
-    case GTA_SF_RELU: return v > 0.f ? v : 0.f;
+    // not v > 0 ? v : 0: NaN compares false and would become a clean 0 (np.maximum and torch.relu give
+    // NaN); bitwise the same result on every other input
+    case GTA_SF_RELU: return v <= 0.f ? 0.f : v;
     case GTA_SF_EXP_LEAKY_RELU: return expf(v > 0.f ? v : 0.2f * v);
     case GTA_SF_ELU: return v > 0.f ? v : expm1f(v);
     case GTA_SF_EXP: return expf(v);
     case GTA_SF_LEAKY_RELU: return v > 0.f ? v : 0.2f * v;
+    // expf(-v) is inf below v = -88.72 and the quotient 0 there, where the sigmoid is still a denormal
+    // (gta.h states it; DESIGN.md 3.5: taking expf(v) there costs every SF epilogue its registers)
     case GTA_SF_SIGMOID: return 1.f / (1.f + expf(-v));
     case GTA_SF_TANH: return tanhf(v);
     case GTA_SF_RECIP: return 1.f / v;

@@ -77,7 +77,38 @@ enum { GTA_BIN_NONE = 0, GTA_BIN_ADD = 1, GTA_BIN_MUL = 2, GTA_BIN_DIV = 3, GTA_
 
 /* Special functions (COMP_TYPE "SF", unit SF_ALU, code/interpreter.py:7).
  * The reference never fixes which function an SF is; these are the build's
- * choices, applied as a post-op of the producing kernel. */
+ * choices, applied as a post-op of the producing kernel.
+ *
+ * Special values of the SFs.  Every site that applies an SF -- gta_apply_node, gta_apply_edge(_flat),
+ * gta_aggregate_expr, gta_edge_softmax, sf_out of gta_gat_aggregate_blocked, the epilogue of every
+ * gta_update_mm* form and both SFs of gta_update_mlp -- computes the same function, bit for bit
+ * (tests/test_gpu_special_values.py).  fp32 denormals are kept, in and out.  NaN in gives NaN out of
+ * EVERY SF, RELU included (so a diverged activation, or a read of a NaN-poisoned guard band, shows in
+ * the output instead of becoming a clean zero).  x > 0 below means "x > 0 and not NaN".
+ *
+ *   SF              value                        -inf   -0    +0    +inf   saturates
+ *   RELU            x <= 0 ? +0 : x              +0     +0    +0    +inf   exact
+ *   LEAKY_RELU      x > 0 ? x : 0.2f * x         -inf   -0    +0    +inf   one fp32 product
+ *   ELU             x > 0 ? x : expm1f(x)        -1     -0    +0    +inf   -1 from x <= -17.33
+ *   EXP             expf(x)                      +0     1     1     +inf   +inf above 88.7228, denormal
+ *                                                                          below -87.3365, 0 below -103.972
+ *   EXP_LEAKY_RELU  expf(x > 0 ? x : 0.2f * x)   +0     1     1     +inf   as EXP, at 5 x the negative x
+ *   SIGMOID         1 / (1 + expf(-x))           +0     0.5   0.5   1      1 from x >= 16.64; denormal
+ *                                                                          below -87.34; +0 from
+ *                                                                          x <= -88.7228 (see below)
+ *   TANH            tanhf(x)                     -1     -0    +0    1      +-1 from |x| >= 9.011
+ *   RECIP           1 / x  (correctly rounded)   -0     -inf  +inf  +0     +-inf for |x| < 2^-128,
+ *                                                                          denormal for |x| > 2^126
+ * Accuracy against the exact function of the fp32 argument (the argument of expf in the leaky form is
+ * the fp32 product 0.2f * x), measured on the MI355X and pinned by the tests at the measured maximum
+ * plus one ulp (tests/special_ref.py SF_ULPS): RELU and LEAKY_RELU exact, RECIP 0.5 ulp, the
+ * transcendental ones per the table in DESIGN.md ("Special values").  A denormal result is measured
+ * in units of 2^-149.
+ * SIGMOID flushes its denormal tail: where expf(-x) overflows (x <= -88.7228) the quotient is +0,
+ * although the exact sigmoid stays a denormal (below 2.9e-39) down to x = -103.97.  Stated, not fixed:
+ * returning expf(x) there costs every kernel with an SF epilogue registers (same section).
+ * The binary ops are IEEE: one correctly rounded fp32 operation each (DIV included), denormals kept,
+ * inf - inf = 0 * inf = 0 / 0 = inf / inf = NaN. */
 enum { GTA_SF_NONE = 0, GTA_SF_RELU = 1, GTA_SF_EXP_LEAKY_RELU = 2 /* exp(leaky_relu(x,0.2)) */,
        GTA_SF_ELU = 3, GTA_SF_EXP = 4, GTA_SF_LEAKY_RELU = 5, GTA_SF_SIGMOID = 6,
        GTA_SF_TANH = 7, GTA_SF_RECIP = 8 };
