@@ -54,6 +54,9 @@ def parser():
                    help="reduce function of the message gathers (their COMP_TYPE); GAT takes ADD only")
     p.add_argument("--stable-softmax", action="store_true",
                    help="overflow-safe attention softmax: exp(score - row max) (GAT; off: the unshifted kernels)")
+    p.add_argument("--gather-dtype", choices=["f32", "bf16"], default="f32",
+                   help="storage type of the node tables the column-blocked aggregates gather (bf16: rounded "
+                        "once, sums in fp32; f32: as they are)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--reps", type=int, default=3, help="runs per layer; the fastest is reported")
     p.add_argument("--model-edges", type=int, default=1 << 20,
@@ -79,6 +82,8 @@ def run(args, device, log=print):
         kw = dict(reorder=args.isReorder, heads=args.heads, metadata=meta, pingpang=args.isPingpang,
                   sinput=args.isSinput, aggregator=getattr(args, "aggregator", "ADD"),
                   stable_softmax=getattr(args, "stable_softmax", False))
+        if getattr(args, "gather_dtype", "f32") == "bf16":
+            kw["gather_dtype"] = torch.bfloat16
         lay = None
         for k, (op_array, tile_size_list) in enumerate(c[:2] for c in cands):
             try:

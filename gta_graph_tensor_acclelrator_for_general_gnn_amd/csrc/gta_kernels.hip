@@ -1027,7 +1027,27 @@ struct AttArgs {
   const float* shift = nullptr;  // SH: [n_rows, H] contiguous row maxima of g(a + b) (k_softmax_shift)
 };
 
-template <int VW, int U, bool WEIGHTED, int NT = 0, bool ATT = false, int SFC = -1, int G = 16, bool SH = false>
+// BF forms of the blocked item kernels (gta_aggregate_blocked_x / gta_gat_aggregate_blocked_x with
+// GTA_BF16): x points at bf16 rows (read as uint16_t; ldx / row_bytes in its units) and four
+// consecutive columns of a gathered row stay two raw dwords (Row4<true>) until the fma, where each
+// element widens exactly (bits << 16).  Same lanes, columns, edge order and fma chain as the fp32
+// form: bitwise its result on the widened table.
+template <bool BF> struct Row4 {
+  typedef float4 type;
+  static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+};
+template <> struct Row4<true> {
+  typedef uint2 type;
+  static __device__ __forceinline__ uint2 zero() { return make_uint2(0u, 0u); }
+};
+__device__ __forceinline__ float4 row4_f32(const float4& r) { return r; }
+__device__ __forceinline__ float4 row4_f32(const uint2& r) {
+  return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
+                     __uint_as_float(r.y & 0xffff0000u));
+}
+
+template <int VW, int U, bool WEIGHTED, int NT = 0, bool ATT = false, int SFC = -1, int G = 16, bool SH = false,
+          bool BF = false>
 // NT bit 0: non-temporal index/weight loads, bit 1: slab stores; SFC >= 0: the ATT special function
 // fixed at compile time (-1: att.sf at run time); G = lanes per item (16: four items per wave,
 // 32: two items per wave -- one 512-B row per half-wave instruction at F = 128); SH: the ATT
@@ -1068,16 +1088,31 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
 #pragma unroll
     for (int s = 0; s < G; s += U) {
       if (c + s >= maxlen) break;
-      float4 xv[U][NQ];
+      typename Row4<BF>::type xv[U][NQ];
       float wu[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int src = bcastG<G>(idxv, s + u);
         const bool ok = c + s + u < len;
         if (ok) {
+          if constexpr (BF) {  // the lane's VW bf16: one 8-B load (VW = 4) or 16-B loads (VW = 16)
+            const uint16_t* pb = reinterpret_cast<const uint16_t*>(x) + static_cast<int64_t>(src) * ldx + col;
+            if constexpr (NQ % 2 == 0) {
+#pragma unroll
+              for (int q = 0; q < NQ; q += 2) {
+                const uint4 t = reinterpret_cast<const uint4*>(pb)[q / 2];
+                xv[u][q] = make_uint2(t.x, t.y);
+                xv[u][q + 1] = make_uint2(t.z, t.w);
+              }
+            } else {
+#pragma unroll
+              for (int q = 0; q < NQ; ++q) xv[u][q] = reinterpret_cast<const uint2*>(pb)[q];
+            }
+          } else {
           const float4* p = reinterpret_cast<const float4*>(x + static_cast<int64_t>(src) * ldx + col);
 #pragma unroll
           for (int q = 0; q < NQ; ++q) xv[u][q] = p[q];
+          }
           if (ATT) {
             const float sv = arow + att.b[static_cast<int64_t>(src) * att.ldb + head];
             if (SH) wu[u] = (SFC >= 0) ? sf_shift(SFC, sv, mrow) : sf_shift(att.sf, sv, mrow);
@@ -1089,7 +1124,7 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
           }
         } else {
 #pragma unroll
-          for (int q = 0; q < NQ; ++q) xv[u][q] = make_float4(0.f, 0.f, 0.f, 0.f);
+          for (int q = 0; q < NQ; ++q) xv[u][q] = Row4<BF>::zero();
           if (WEIGHTED || ATT) wu[u] = 0.f;
         }
       }
@@ -1097,7 +1132,8 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
       for (int u = 0; u < U; ++u) {
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-          const float* xf = reinterpret_cast<const float*>(&xv[u][q]);
+          const float4 xw = row4_f32(xv[u][q]);
+          const float* xf = reinterpret_cast<const float*>(&xw);
 #pragma unroll
           for (int t = 0; t < 4; ++t)
             acc[4 * q + t] = (WEIGHTED || ATT) ? fmaf(wu[u], xf[t], acc[4 * q + t]) : acc[4 * q + t] + xf[t];
@@ -1154,7 +1190,9 @@ __device__ __forceinline__ float xmask4(float v, bool odd_quad) {
 // reaches the head's lanes by the same quad broadcasts, picked per lane by head parity.  The same
 // weights enter the same fma chain: bitwise equal to the two-load form.  (the alpha
 // loads were ~19 % of the kernel's vector-memory instructions; the texture path is its bound.)
-template <bool WEIGHTED, int NT, bool W1 = false, bool A1 = false>
+// BF: bf16 rows in the same lane layout with half-width loads -- 32 lanes x 8 B, one 256-B row per
+// half-wave instruction (row_bytes = 2 ldx; the host guards are restated for 2-byte elements).
+template <bool WEIGHTED, int NT, bool W1 = false, bool A1 = false, bool BF = false>
 __global__ void __launch_bounds__(kBlock)
 k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
           uint32_t row_bytes, const float* __restrict__ w, int64_t ldw, float* __restrict__ slabs,
@@ -1171,7 +1209,8 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   const int maxlen = __builtin_amdgcn_readfirstlane(max(len, other));
   const int minlen = __builtin_amdgcn_readfirstlane(min(len, other));
   if (maxlen == 0) return;
-  const uint32_t colb = static_cast<uint32_t>(l32) * 16u;
+  typedef typename Row4<BF>::type XR;
+  const uint32_t colb = static_cast<uint32_t>(l32) * (BF ? 8u : 16u);
   const char* xb = reinterpret_cast<const char*>(x);
   const int h = l32 >> 2, q = l32 & 3;
   const int ldw32 = static_cast<int>(ldw);
@@ -1190,8 +1229,8 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   // once), bit 1: non-temporal slab stores
   auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
   auto ldw_ = [&](const float* p) { return (NT & 4) ? __builtin_nontemporal_load(p) : *p; };
-  auto row = [&](int src) -> float4 {
-    return *reinterpret_cast<const float4*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
+  auto row = [&](int src) -> XR {
+    return *reinterpret_cast<const XR*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
   };
   int idxv = (l32 < len) ? ldi(ic + l32) : 0;
   float wv = (W1 && l32 < len) ? ldw_(wc + l32 * ldw32) : 0.f;  // W1: this chunk's weights, lane = edge
@@ -1201,7 +1240,7 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
 #pragma unroll
     for (int s = 0; s < G; s += U) {
       if (c + s >= maxlen) break;
-      float4 xv[U];
+      XR xv[U];
       float wu[U];
       if (c + s + U <= minlen) {  // full step for both items: no masks
 #pragma unroll
@@ -1243,20 +1282,21 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
               wu[u] = W1 ? __int_as_float(bcastG<G>(__float_as_int(wv), s + u))
                          : (A1 ? wat(woff + static_cast<uint32_t>(s + u) * wrow) : ldw_(wc + (s + u) * ldw32));
           } else {
-            xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            xv[u] = Row4<BF>::zero();
             if (WEIGHTED) wu[u] = 0.f;
           }
         }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
+        const float4 xw = row4_f32(xv[u]);
         if (WEIGHTED) {
-          acc[0] = fmaf(wu[u], xv[u].x, acc[0]);
-          acc[1] = fmaf(wu[u], xv[u].y, acc[1]);
-          acc[2] = fmaf(wu[u], xv[u].z, acc[2]);
-          acc[3] = fmaf(wu[u], xv[u].w, acc[3]);
+          acc[0] = fmaf(wu[u], xw.x, acc[0]);
+          acc[1] = fmaf(wu[u], xw.y, acc[1]);
+          acc[2] = fmaf(wu[u], xw.z, acc[2]);
+          acc[3] = fmaf(wu[u], xw.w, acc[3]);
         } else {
-          acc[0] += xv[u].x; acc[1] += xv[u].y; acc[2] += xv[u].z; acc[3] += xv[u].w;
+          acc[0] += xw.x; acc[1] += xw.y; acc[2] += xw.z; acc[3] += xw.w;
         }
       }
     }
@@ -1505,7 +1545,8 @@ k_agg_h32pf(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_i
 // reduce skips its row (k_seg_reduce_att with skip_single).
 // SH: the shifted weight, v = expf(leaky_relu(a + b) - shift[row, h]); the row's shift is loaded
 // once beside a[row, h], the 2-SF step and the direct epilogue are unchanged.
-template <int NT, bool SH = false>
+// BF: bf16 x rows as in k_agg_h32<BF> (the score tables stay fp32).
+template <int NT, bool SH = false, bool BF = false>
 __global__ void __launch_bounds__(kBlock)
 k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
           uint32_t row_bytes, const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
@@ -1526,14 +1567,15 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   const int minlen = __builtin_amdgcn_readfirstlane(min(len, other));
   if (maxlen == 0) return;
   const int h = l32 >> 2, q = l32 & 3;
-  const uint32_t colb = static_cast<uint32_t>(l32) * 16u, hb = static_cast<uint32_t>(h) * 4u;
+  typedef typename Row4<BF>::type XR;
+  const uint32_t colb = static_cast<uint32_t>(l32) * (BF ? 8u : 16u), hb = static_cast<uint32_t>(h) * 4u;
   const char* xb = reinterpret_cast<const char*>(x);
   const char* bb = reinterpret_cast<const char*>(b);
   const float arow = (len > 0) ? a[static_cast<int64_t>(it.row) * lda + h] : 0.f;
   const float mrow = (SH && len > 0) ? shift[static_cast<int64_t>(it.row) * 8 + h] : 0.f;
   auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
-  auto row = [&](int src) -> float4 {
-    return *reinterpret_cast<const float4*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
+  auto row = [&](int src) -> XR {
+    return *reinterpret_cast<const XR*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
   };
   auto score = [&](int src) -> float {
     const float sv = arow + *reinterpret_cast<const float*>(bb + (__umul24(static_cast<uint32_t>(src), brow_bytes) + hb));
@@ -1548,7 +1590,7 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
 #pragma unroll
     for (int s = 0; s < G; s += U) {
       if (c + s >= maxlen) break;
-      float4 xv[U];
+      XR xv[U];
       float wu[U];
       if (c + s + U <= minlen) {  // full step for both items: no masks
         int src[U];
@@ -1576,17 +1618,18 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
             wu[u] = score(src);
             ssum += wu[u];
           } else {
-            xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            xv[u] = Row4<BF>::zero();
             wu[u] = 0.f;
           }
         }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        acc[0] = fmaf(wu[u], xv[u].x, acc[0]);
-        acc[1] = fmaf(wu[u], xv[u].y, acc[1]);
-        acc[2] = fmaf(wu[u], xv[u].z, acc[2]);
-        acc[3] = fmaf(wu[u], xv[u].w, acc[3]);
+        const float4 xw = row4_f32(xv[u]);
+        acc[0] = fmaf(wu[u], xw.x, acc[0]);
+        acc[1] = fmaf(wu[u], xw.y, acc[1]);
+        acc[2] = fmaf(wu[u], xw.z, acc[2]);
+        acc[3] = fmaf(wu[u], xw.w, acc[3]);
       }
     }
     idxv = idxn;
@@ -4794,35 +4837,44 @@ int64_t gta_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, int64
   return blocked_max_items(n_rows, nnz, static_cast<int>(blocks), item_edges) * F * static_cast<int64_t>(sizeof(float));
 }
 
-int gta_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols, int64_t nnz,
-                          const float* x, int64_t ldx, int64_t F, const float* w, int64_t ldw, int64_t heads,
-                          const float* row_scale, float* y, int64_t ldy, int accumulate, const void* plan,
-                          int64_t blocks, int64_t item_edges, void* workspace, void* stream) {
+// gta_aggregate_blocked (who "aggregate_blocked", GTA_F32) and gta_aggregate_blocked_x: one argument
+// check, one dispatch; the fp32 launches are the instantiations they always were.  bf16 rows
+// (xv, ldx in bf16 elements) take the multi-item forms only -- the <..., BF = true> twins of the
+// fp32 launches; the scalar-prefetch form (seg_pf) has no bf16 twin and is not selected for them.
+static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr, const int32_t* indices, int64_t n_rows,
+                                  int64_t n_cols, int64_t nnz, const void* xv, int64_t ldx, int64_t F, int x_dtype,
+                                  const float* w, int64_t ldw, int64_t heads, const float* row_scale, float* y,
+                                  int64_t ldy, int accumulate, const void* plan, int64_t blocks, int64_t item_edges,
+                                  void* workspace, void* stream) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
   if (n_rows < 0 || nnz < 0 || F <= 0 || blocks < 1 || blocks > 63 || item_edges < 1)
-    return fail(GTA_ERR_ARG, "aggregate_blocked: bad sizes");
+    return fail(GTA_ERR_ARG, who + ": bad sizes");
+  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, who + ": x_dtype must be F32 or BF16");
   if (n_rows == 0) return GTA_OK;
-  if (!indptr || !x || !y || !plan) return fail(GTA_ERR_ARG, "aggregate_blocked: bad arguments");
+  if (!indptr || !xv || !y || !plan) return fail(GTA_ERR_ARG, who + ": bad arguments");
+  const bool bf = x_dtype == GTA_BF16;
+  const float* x = static_cast<const float*>(xv);  // bf: bf16 rows, read as such by the BF kernels only
   int gl = 0, vw = 0;
   for (int c : {4, 2, 1}) {
-    if (F == static_cast<int64_t>(kWave) * c && ldx % c == 0 && ldy % c == 0 && aligned(x, 4 * c) && aligned(y, 4 * c)) {
+    if (F == static_cast<int64_t>(kWave) * c && (bf || (ldx % c == 0 && aligned(x, 4 * c))) && ldy % c == 0 &&
+        aligned(y, 4 * c)) {
       vw = c;
       break;
     }
   }
-  if (!vw) return fail(GTA_ERR_UNSUPPORTED, "aggregate_blocked: F must be 64, 128 or 256 (one edge per wave row)");
+  if (!vw) return fail(GTA_ERR_UNSUPPORTED, who + ": F must be 64, 128 or 256 (one edge per wave row)");
   bool gl_ok = true;  // head layout of the one-item-per-wave forms
   if (w) {
-    if (heads <= 0 || F % heads) return fail(GTA_ERR_ARG, "aggregate_blocked: heads must divide F");
+    if (heads <= 0 || F % heads) return fail(GTA_ERR_ARG, who + ": heads must divide F");
     gl = static_cast<int>(F / heads) / vw;
     gl_ok = (F / heads) % vw == 0 && (gl == 4 || gl == 8 || gl == 16);
   }
-  const char* gl_msg = "aggregate_blocked: (F/heads)/VW must be 4, 8 or 16 (or quarter-wave lanes per head 1..16)";
+  const std::string gl_msg = who + ": (F/heads)/VW must be 4, 8 or 16 (or quarter-wave lanes per head 1..16)";
   const int B = static_cast<int>(blocks);
   const int64_t mi = blocked_max_items(n_rows, nnz, B, item_edges);
   BlockedView v = blocked_view(const_cast<void*>(plan), n_rows, B, mi);
   hipStream_t s = S(stream);
-  if (!workspace && nnz > 0) return fail(GTA_ERR_ARG, "aggregate_blocked: needs the slab workspace");
+  if (!workspace && nnz > 0) return fail(GTA_ERR_ARG, who + ": needs the slab workspace");
   // one launch over the plan's items into per-item slab rows, then the ordered reduce
   const RowItems ri{v.row_ptr, v.row_items};
   float* slabs = static_cast<float*>(workspace);
@@ -4834,18 +4886,22 @@ int gta_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int64_t
   const int lph = w ? static_cast<int>((F / heads) / vq) : 0;
   // multi-item waves (F = 64 / 256: four 16-lane items; F = 128: two 32-lane items, one 512-B row per
   // half-wave instruction) when rows are 16-B aligned and the heads fit the lanes; else one item per wave
-  const bool quarter = (vq == 4 || vq == 8 || vq == 16) && ldx % 4 == 0 && aligned(x, 16) &&
+  const bool quarter = (vq == 4 || vq == 8 || vq == 16) && ldx % (bf ? 8 : 4) == 0 && aligned(x, 16) &&
                        (!w || ((F / heads) % vq == 0 && lph >= 1 && 16 % lph == 0));
+  if (bf && !quarter)  // the one-item-per-wave fallback (k_agg_seg2d) has no bf16 twin
+    return fail(GTA_ERR_UNSUPPORTED, who + ": bf16 rows need x 16-B aligned, ldx % 8 == 0 and heads that fit the "
+                                           "multi-item forms (F/heads a multiple of F/16, lanes per head dividing 16)");
   const int phase = tuning().seg_phase;
+  const unsigned xe = bf ? 2u : 4u;  // bytes per gathered element
   if (items == 0 || phase == 2) {
     // no edges: no items; the reduce below writes the (empty) rows (phase 2: the reduce only)
-  } else if (quarter && vq == 8) {  // F = 128: half-wave items, 32 lanes x float4
+  } else if (quarter && vq == 8) {  // F = 128: half-wave items, 32 lanes x float4 (bf16: x 8 B)
     const int lph32 = w ? static_cast<int>((F / heads) / 4) : 0;
     const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
     const bool lean = tuning().seg_lean && n_cols < (1 << 24) &&
-                      static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * 4u < (1ull << 32) &&
+                      static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * xe < (1ull << 32) &&
                       (!w || lph32 == 4 || (heads == 1 && tuning().seg_lean_w1 && ldw < (int64_t(1) << 24)));
-    const uint32_t rb = static_cast<uint32_t>(ldx * 4);
+    const uint32_t rb = static_cast<uint32_t>(ldx * xe);
     // NT template bits: 1 = non-temporal index loads, 2 = non-temporal slab stores (measured -0.5 % / -1 %;
     // non-temporal weight loads +3 %: profiles/r02_nt_bits_ab.json)
     if (lean) {
@@ -4853,7 +4909,12 @@ int gta_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int64_t
                       static_cast<uint64_t>(nnz) * static_cast<uint64_t>(ldw) * 4u < (1ull << 32);
       const int pf = tuning().seg_pf;
       const uint32_t wbytes = static_cast<uint32_t>(nnz * ldw * 4), ibytes = static_cast<uint32_t>(nnz * 4);
-      if (w && heads == 1) k_agg_h32<true, 2, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
+      if (bf) {
+        if (w && heads == 1) k_agg_h32<true, 2, true, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
+        else if (a1) k_agg_h32<true, 3, false, true, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
+        else if (w) k_agg_h32<true, 3, false, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
+        else k_agg_h32<false, 2, false, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
+      } else if (w && heads == 1) k_agg_h32<true, 2, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
       else if (a1 && ldw == 8 && pf >= 1 && pf <= 5) {
 #define GTA_PF(PFB_, PD_) k_agg_h32pf<3, PFB_, PD_><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its, wbytes, ibytes)
         if (pf == 1) GTA_PF(64, 0); else if (pf == 2) GTA_PF(128, 0); else if (pf == 3) GTA_PF(64, 1); else if (pf == 4) GTA_PF(128, 1);
@@ -4864,14 +4925,20 @@ int gta_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int64_t
       else k_agg_h32<false, 2><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
       GTA_LAUNCHED("k_agg_h32");
     } else {
-      if (w) k_agg_seg4<4, 8, true, 2, false, -1, 32><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph32, slabs, its);
+      if (bf && w) k_agg_seg4<4, 8, true, 2, false, -1, 32, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph32, slabs, its);
+      else if (bf) k_agg_seg4<4, 8, false, 2, false, -1, 32, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, 0, slabs, its);
+      else if (w) k_agg_seg4<4, 8, true, 2, false, -1, 32><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph32, slabs, its);
       else k_agg_seg4<4, 8, false, 2, false, -1, 32><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, 0, slabs, its);
       GTA_LAUNCHED("k_agg_seg4<half>");
     }
   } else if (quarter) {  // F = 64 / 256: quarter-wave items
     const dim3 g4(static_cast<unsigned>((items + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock)));
 #define GTA_SEG4(VW_, U_)                                                                               \
-  if (w) k_agg_seg4<VW_, U_, true><<<g4, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph, slabs, its); \
+  if (bf && w) k_agg_seg4<VW_, U_, true, 0, false, -1, 16, false, true><<<g4, blk2, 0, s>>>(           \
+      indices, nit, x, ldx, w, ldw, lph, slabs, its);                                                  \
+  else if (bf) k_agg_seg4<VW_, U_, false, 0, false, -1, 16, false, true><<<g4, blk2, 0, s>>>(          \
+      indices, nit, x, ldx, w, ldw, lph, slabs, its);                                                  \
+  else if (w) k_agg_seg4<VW_, U_, true><<<g4, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph, slabs, its); \
   else k_agg_seg4<VW_, U_, false><<<g4, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph, slabs, its)
     if (vq == 4) { GTA_SEG4(4, 4); } else { GTA_SEG4(16, 2); }
 #undef GTA_SEG4
@@ -4899,6 +4966,22 @@ int gta_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int64_t
   return GTA_OK;
 }
 
+int gta_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                          const float* x, int64_t ldx, int64_t F, const float* w, int64_t ldw, int64_t heads,
+                          const float* row_scale, float* y, int64_t ldy, int accumulate, const void* plan,
+                          int64_t blocks, int64_t item_edges, void* workspace, void* stream) {
+  return aggregate_blocked_impl("aggregate_blocked", indptr, indices, n_rows, n_cols, nnz, x, ldx, F, GTA_F32, w, ldw,
+                                heads, row_scale, y, ldy, accumulate, plan, blocks, item_edges, workspace, stream);
+}
+
+int gta_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                            const void* x, int64_t ldx, int64_t F, int x_dtype, const float* w, int64_t ldw,
+                            int64_t heads, const float* row_scale, float* y, int64_t ldy, int accumulate,
+                            const void* plan, int64_t blocks, int64_t item_edges, void* workspace, void* stream) {
+  return aggregate_blocked_impl("aggregate_blocked_x", indptr, indices, n_rows, n_cols, nnz, x, ldx, F, x_dtype, w,
+                                ldw, heads, row_scale, y, ldy, accumulate, plan, blocks, item_edges, workspace, stream);
+}
+
 int64_t gta_gat_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, int64_t blocks, int64_t F,
                                                   int64_t heads, int64_t item_edges) {
   if (n_rows < 0 || nnz < 0 || blocks < 1 || blocks > 63 || F <= 0 || heads <= 0 || item_edges < 1)
@@ -4907,11 +4990,12 @@ int64_t gta_gat_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, i
          static_cast<int64_t>(sizeof(float));
 }
 
-// gta_gat_aggregate_blocked (shifted false) and gta_gat_aggregate_blocked_shifted: one argument check,
-// one dispatch; the unshifted launches are the instantiations they always were.
+// gta_gat_aggregate_blocked (shifted false), gta_gat_aggregate_blocked_shifted and
+// gta_gat_aggregate_blocked_x: one argument check, one dispatch; the fp32 launches are the
+// instantiations they always were, bf16 rows (xv, ldx in bf16 elements) launch their <..., BF = true> twins.
 static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64_t* indptr, const int32_t* indices,
-                                      int64_t n_rows, int64_t n_cols, int64_t nnz, const float* x, int64_t ldx,
-                                      int64_t F, const float* a_dst, int64_t lda, const float* b_src, int64_t ldb,
+                                      int64_t n_rows, int64_t n_cols, int64_t nnz, const void* xv, int64_t ldx,
+                                      int64_t F, int x_dtype, const float* a_dst, int64_t lda, const float* b_src, int64_t ldb,
                                       int64_t heads, int sf, int normalize, int sf_out, float* y, int64_t ldy,
                                       float* sums, const void* plan, int64_t blocks, int64_t item_edges,
                                       void* workspace, const float* shift, void* stream) {
@@ -4919,6 +5003,10 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
   if (n_rows < 0 || nnz < 0 || blocks < 1 || blocks > 63 || heads <= 0 || lda < heads || ldb < heads ||
       item_edges < 1 || sf_out < GTA_SF_NONE || sf_out > GTA_SF_RECIP)
     return fail(GTA_ERR_ARG, std::string(who) + ": bad sizes");
+  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16)
+    return fail(GTA_ERR_ARG, std::string(who) + ": x_dtype must be F32 or BF16");
+  const bool bf = x_dtype == GTA_BF16;
+  const float* x = static_cast<const float*>(xv);  // bf: bf16 rows, read as such by the BF kernels only
   if (shifted && !shift) return fail(GTA_ERR_ARG, std::string(who) + ": shift is required");
   if (shifted && !sf_is_exp_form(sf))
     return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": sf must be EXP_LEAKY_RELU or EXP");
@@ -4926,9 +5014,10 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
   if (!indptr || !x || !a_dst || !b_src || !y || !plan || (!workspace && nnz > 0))
     return fail(GTA_ERR_ARG, std::string(who) + ": bad arguments");
   const int vq = static_cast<int>(F / 16);
-  if ((F != 64 && F != 128 && F != 256) || F % heads || (F / heads) % vq || ldx % 4 || !aligned(x, 16) ||
+  if ((F != 64 && F != 128 && F != 256) || F % heads || (F / heads) % vq || ldx % (bf ? 8 : 4) || !aligned(x, 16) ||
       ldy % (F / 64) || !aligned(y, 4 * (F / 64)))
-    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": F in {64,128,256}, 16-B rows, F/heads a multiple of F/16");
+    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": F in {64,128,256}, 16-B rows (bf16: ldx % 8 == 0), F/heads "
+                                                          "a multiple of F/16");
   const int lph = static_cast<int>((F / heads) / vq);
   if (lph < 1 || 16 % lph) return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": lanes per head must divide 16");
   const int B = static_cast<int>(blocks);
@@ -4954,19 +5043,35 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
       indices, nit, x, ldx, nullptr, 0, lph, slabs, it, att);                                            \
   else k_agg_seg4<VW_, U_, false, 0, true><<<g4, blk, 0, s>>>(indices, nit, x, ldx, nullptr, 0, lph, slabs, \
                                                              it, att)
+// the bf16 twins: G_ lanes per item on grid GR_, lanes per head LPH_
+#define GTA_ATT_BF(VW_, U_, G_, GR_, LPH_)                                                                        \
+  if (shifted && elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU, G_, true, true><<<GR_, blk, 0, s>>>( \
+      indices, nit, x, ldx, nullptr, 0, LPH_, slabs, it, att);                                           \
+  else if (shifted) k_agg_seg4<VW_, U_, false, 0, true, -1, G_, true, true><<<GR_, blk, 0, s>>>(                 \
+      indices, nit, x, ldx, nullptr, 0, LPH_, slabs, it, att);                                           \
+  else if (elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU, G_, false, true><<<GR_, blk, 0, s>>>( \
+      indices, nit, x, ldx, nullptr, 0, LPH_, slabs, it, att);                                           \
+  else k_agg_seg4<VW_, U_, false, 0, true, -1, G_, false, true><<<GR_, blk, 0, s>>>(                             \
+      indices, nit, x, ldx, nullptr, 0, LPH_, slabs, it, att)
   const int lph32 = static_cast<int>((F / heads) / 4);
   const bool lean = tuning().att_lean && elr && F == 128 && heads == 8 && n_cols < (1 << 24) &&
-                    static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * 4u < (1ull << 32) &&
+                    static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * (bf ? 2u : 4u) < (1ull << 32) &&
                     static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldb) * 4u < (1ull << 32);
   if (lean) {
     const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
-    const uint32_t rb = static_cast<uint32_t>(ldx * 4), bbytes = static_cast<uint32_t>(ldb * 4);
+    const uint32_t rb = static_cast<uint32_t>(ldx * (bf ? 2 : 4)), bbytes = static_cast<uint32_t>(ldb * 4);
     // single-item rows are common only when few blocks cut the rows (low degree, B <= 2); above
     // that the row_ptr reads at every item's end cost more than the rare direct writes save
     const bool direct = (tuning().att_direct == 2 || (tuning().att_direct == 1 && B <= 2)) && ldy % 4 == 0 && aligned(y, 16);
     skip_single = direct;
     const int64_t* rp = direct ? v.row_ptr : nullptr;
-    if (shifted)
+    if (bf && shifted)
+      k_att_h32<2, true, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp,
+                                                   normalize, y, ldy, sums, sf_out, shift);
+    else if (bf)
+      k_att_h32<2, false, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp,
+                                                    normalize, y, ldy, sums, sf_out);
+    else if (shifted)
       k_att_h32<2, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp, normalize,
                                              y, ldy, sums, sf_out, shift);
     else
@@ -4974,7 +5079,8 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
                                        ldy, sums, sf_out);  // NT bit 2: non-temporal slab stores
   } else if (F == 128 && (F / heads) % 4 == 0 && lph32 >= 1 && 32 % lph32 == 0) {
     const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
-    if (shifted && elr) k_agg_seg4<4, 8, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 32, true><<<g2h, blk, 0, s>>>(
+    if (bf) { GTA_ATT_BF(4, 8, 32, g2h, lph32); }
+    else if (shifted && elr) k_agg_seg4<4, 8, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 32, true><<<g2h, blk, 0, s>>>(
         indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
     else if (shifted) k_agg_seg4<4, 8, false, 0, true, -1, 32, true><<<g2h, blk, 0, s>>>(
         indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
@@ -4982,7 +5088,10 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
         indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
     else k_agg_seg4<4, 8, false, 0, true, -1, 32><<<g2h, blk, 0, s>>>(indices, nit, x, ldx, nullptr, 0,
                                                                       lph32, slabs, it, att);
+  } else if (bf) {
+    if (vq == 4) { GTA_ATT_BF(4, 4, 16, g4, lph); } else { GTA_ATT_BF(16, 2, 16, g4, lph); }
   } else if (vq == 4) { GTA_ATT(4, 4); } else { GTA_ATT(16, 2); }
+#undef GTA_ATT_BF
 #undef GTA_ATT
   GTA_LAUNCHED("k_agg_seg4<att>");
   }
@@ -5002,7 +5111,7 @@ int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int
                               float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks, int64_t item_edges,
                               void* workspace, void* stream) {
   return gat_aggregate_blocked_impl("gat_aggregate_blocked", false, indptr, indices, n_rows, n_cols, nnz, x, ldx, F,
-                                    a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums, plan, blocks,
+                                    GTA_F32, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums, plan, blocks,
                                     item_edges, workspace, nullptr, stream);
 }
 
@@ -5013,8 +5122,18 @@ int gta_gat_aggregate_blocked_shifted(const int64_t* indptr, const int32_t* indi
                                       int64_t blocks, int64_t item_edges, void* workspace, const float* shift,
                                       void* stream) {
   return gat_aggregate_blocked_impl("gat_aggregate_blocked_shifted", true, indptr, indices, n_rows, n_cols, nnz, x,
-                                    ldx, F, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums, plan,
-                                    blocks, item_edges, workspace, shift, stream);
+                                    ldx, F, GTA_F32, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums,
+                                    plan, blocks, item_edges, workspace, shift, stream);
+}
+
+int gta_gat_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                                int64_t nnz, const void* x, int64_t ldx, int64_t F, int x_dtype, const float* a_dst,
+                                int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf, int normalize,
+                                int sf_out, float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks,
+                                int64_t item_edges, void* workspace, const float* shift, void* stream) {
+  return gat_aggregate_blocked_impl("gat_aggregate_blocked_x", shift != nullptr, indptr, indices, n_rows, n_cols, nnz,
+                                    x, ldx, F, x_dtype, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy,
+                                    sums, plan, blocks, item_edges, workspace, shift, stream);
 }
 
 }  // extern "C"

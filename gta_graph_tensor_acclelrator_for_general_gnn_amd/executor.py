@@ -172,7 +172,7 @@ MAX_MATERIALIZE_BYTES = 96 << 30  # refuse to materialise a single edge tensor l
 
 class Executor:
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, dist=None,
-                 softmax_shift=None):
+                 softmax_shift=None, gather_dtype=None):
         self.g = opgraph
         # dist (distributed.Comm): node tensors are this rank's row block; gathers are
         # reduce-scattered to it and dst-side scatters all-gather it (distributed.py)
@@ -224,6 +224,21 @@ class Executor:
         #   table of a chain is built once, on first use, and handed to both of its launches
         self.softmax_shift = SOFTMAX_SHIFT if softmax_shift is None else bool(softmax_shift)
         self._att_shift = {}  # score op A -> Lazy shift table [n, H] (beside _att_state)
+        #   gather_dtype: None (the default: nothing changes), or torch.bfloat16 -- the storage type of
+        #   the node tables the column-blocked kernels gather.  An fp32 table that a SpMM-form ADD
+        #   aggregate (_spmm, mode src, weighted or not) would gather column-blocked, or that the fused
+        #   attention aggregate (_eval_attention) gathers, is rounded once to bf16 (RNE, Tensor.to:
+        #   plumbing, capturable) and gathered as bf16 -- half the row bytes, every sum still fp32,
+        #   bitwise the fp32 run on the rounded table (gta_aggregate_blocked_x).  A table that is bf16
+        #   already (a bf16 model input) takes the blocked form by the same size rule, with no cast.
+        #   One cast per table value, shared by its consumers (_gather_cast; gather_casts counts
+        #   them).  Left as they are: the row-chunked form (tables under the size gate), MAX / MIN /
+        #   expression gathers, self-term forms, ORDER C and distributed.py.
+        if gather_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError(f"gather_dtype: None, torch.float32 or torch.bfloat16, not {gather_dtype}")
+        self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
+        self.gather_casts = 0
+        self._gather_cache = {}  # id(table) -> (table, its version, the bf16 copy): identity checked on use
         #   mm_first: a gather whose only consumer is a narrowing applynode MM is executed as
         #   MM-then-aggregate (sum_e w_e x_src) W == sum_e w_e (x W)_src -- the layer's output
         #   to fp32 rounding, the gather's own value computed only if something asks for it
@@ -861,9 +876,10 @@ class Executor:
         shift = self._att_shift.get(pat["A"])
         x = sv.t
         F, H = x.shape[1], a.shape[1]
-        if x.dtype != torch.float32 or not ops.BlockedPlan.supports_att(F, H):
+        if x.dtype not in ops.BlockedPlan.DTYPES or not ops.BlockedPlan.supports_att(F, H):
             return None
-        B = self.attention_blocks or ops.BlockedPlan.auto_blocks(self.graph, F)
+        xe = 2 if self.gather_dtype == torch.bfloat16 else x.element_size()  # bytes per gathered element
+        B = self.attention_blocks or ops.BlockedPlan.auto_blocks(self.graph, F, xe)
         # the lean fused kernel (F = 128, 8 heads) beats softmax + aggregate even unblocked (B = 1:
         # Flickr 102 vs 168 us; the round-4 probe, profiles/r04/layer_bench_*.log); other shapes need a blocked table
         lean = F == 128 and H == 8
@@ -874,14 +890,15 @@ class Executor:
         gv = self.values.get(G)
         want = not norm and isinstance(gv, Lazy) and gv.v is None
         E, n = self.graph.nnz, self.graph.n_rows
+        x = self._gather_cast(x)
         if shift is not None:
             y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
                                                 sf_out=sf_out, shift=shift.force())
-            self._count(E * (4 + 4 * F + 4 * H) + n * (8 + 4 * F + 8 * H))
+            self._count(E * (4 + xe * F + 4 * H) + n * (8 + 4 * F + 8 * H))
         else:
             y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
                                                 sf_out=sf_out)
-            self._count(E * (4 + 4 * F + 4 * H) + n * (8 + 4 * F + 4 * H))
+            self._count(E * (4 + xe * F + 4 * H) + n * (8 + 4 * F + 4 * H))
         if want:
             self.values[G] = NodeT(sums)
         return NodeT(y)
@@ -1222,6 +1239,11 @@ class Executor:
         and indices come from (default the layer's CSR; a CSC view for the ORDER-C gathers)."""
         g = self.graph if graph is None else graph
         B = self._blocked_blocks(xt, mode, 0 if wt is None else wt.shape[1], g)
+        if B and self_term is None and graph is None:
+            xb = self._gather_cast(xt)
+            if xb is not xt:  # the callers count xt's rows per edge: take off what the narrower rows save
+                self.alg_bytes -= g.nnz * xt.shape[1] * (xt.element_size() - xb.element_size())
+                xt = xb
         if self_term is not None:
             xs, sc = self_term
             if B or xs.dtype != xt.dtype or xs.shape[1] != xt.shape[1] or xs.shape[0] < g.n_rows:
@@ -1236,15 +1258,37 @@ class Executor:
         form: a source table of at least blocked_min_table_bytes (its own element size) of a dtype
         and width the blocked kernels take."""
         g = self.graph if graph is None else graph
-        if not (mode == "src" and self.blocked_blocks and xt.dtype in ops.BlockedPlan.DTYPES
-                and xt.shape[0] * xt.shape[1] * xt.element_size() >= self.blocked_min_table_bytes
-                and ops.BlockedPlan.supports(xt.shape[1], heads, xt.dtype)):
+        # the table as it will be gathered: with gather_dtype bf16, _spmm rounds an fp32 table of the
+        # layer's own CSR (not of the ORDER-C views) to bf16, and a bf16 table is taken as it is; with
+        # the option off only fp32 tables take the blocked form
+        on = self.gather_dtype == torch.bfloat16
+        dt = torch.bfloat16 if on and xt.dtype == torch.float32 and graph is None else xt.dtype
+        es = 2 if dt == torch.bfloat16 else xt.element_size()
+        if not (mode == "src" and self.blocked_blocks and (dt == torch.float32 or (on and dt == torch.bfloat16))
+                and xt.shape[0] * xt.shape[1] * es >= self.blocked_min_table_bytes
+                and ops.BlockedPlan.supports(xt.shape[1], heads, dt)):
             return 0
         B = self.blocked_blocks
         if B == "auto":
-            B = ops.BlockedPlan.auto_blocks(g, xt.shape[1], xt.element_size())
+            B = ops.BlockedPlan.auto_blocks(g, xt.shape[1], es)
             B = B if B >= 4 else 0
         return B if B and g.blocked_plan(B).sorted else 0
+
+    def _gather_cast(self, t):
+        """The node table t as the blocked kernels gather it under gather_dtype: t itself (no option,
+        or t already of that type), else its RNE rounding to bf16 -- made once per table value and
+        shared by its consumers.  The cache entry holds t itself and is used only for that very
+        tensor at the version it was cast at, so an address reused by another tensor never hits."""
+        if self.gather_dtype != torch.bfloat16 or t.dtype != torch.float32:
+            return t
+        ent = self._gather_cache.get(id(t))
+        if ent is not None and ent[0] is t and ent[1] == t._version:
+            return ent[2]
+        tb = ops.pitched(t.to(torch.bfloat16))
+        self._count(t.shape[0] * t.shape[1] * 6)
+        self.gather_casts += 1
+        self._gather_cache[id(t)] = (t, t._version, tb)
+        return tb
 
     def _unweighted(self, x):
         if isinstance(x, Scat):
@@ -1659,13 +1703,14 @@ def set_auto_graph(flag):
         clear_auto_graphs()
 
 
-def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=None):
+def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=None, gather_dtype=None):
     """-> a GraphedRun to replay for this call, or None (run eagerly)."""
     if ops.Tuning.attached(torch.cuda.current_stream(graph.device)):
         return None  # a knob set on this stream: every call reads it (gta.h), so no cached graph
     refs = (opgraph, stream, graph, semantics)
     shifted = SOFTMAX_SHIFT if softmax_shift is None else bool(softmax_shift)
-    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted), id(tensors), ops.knob_state())
+    gdt = None if gather_dtype == torch.float32 else gather_dtype
+    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt), id(tensors), ops.knob_state())
     ent = _AUTO_FAST.get(fkey)
     if ent is not None and not (ent.src is tensors and all(a is b for a, b in zip(ent.refs, refs)) and
                                 len(tensors) == len(ent.tensors) and
@@ -1699,7 +1744,7 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_
         before = torch.cuda.memory_reserved(graph.device)
         try:
             ent.run = GraphedRun(opgraph, stream, graph, ent.tensors, semantics, plan_chunk, warmup=1,
-                                 softmax_shift=shifted)
+                                 softmax_shift=shifted, gather_dtype=gdt)
         except Exception:  # something in this stream is not capturable: stay eager for this key
             ent.failed = True
             torch.cuda.synchronize(graph.device)
@@ -1728,13 +1773,14 @@ def _evict_pools(keep):
 
 
 def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, sync=True, trace=False,
-               softmax_shift=None):
-    """softmax_shift: Executor.softmax_shift for this call (None: the module's SOFTMAX_SHIFT)."""
+               softmax_shift=None, gather_dtype=None):
+    """softmax_shift: Executor.softmax_shift for this call (None: the module's SOFTMAX_SHIFT).
+    gather_dtype: Executor.gather_dtype for this call (None: tables are gathered as they are)."""
     dev = graph.device
     if not AUTO_GRAPH and _AUTO:
         clear_auto_graphs()
     if AUTO_GRAPH and not trace and dev.type == "cuda" and graph.nnz <= AUTO_GRAPH_MAX_EDGES:
-        gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift)
+        gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift, gather_dtype)
         if gr is not None:
             if sync:
                 torch.cuda.synchronize(dev)
@@ -1744,7 +1790,8 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
                 torch.cuda.synchronize(dev)
             ex = gr.executor
             return ExecResult(ex.values, outputs, time.perf_counter() - t0, ex.alg_bytes, ex.launches), ex
-    ex = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift)
+    ex = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
+                  gather_dtype=gather_dtype)
     ex.trace = trace
     sync = sync and dev.type == "cuda"
     if sync:
@@ -1932,7 +1979,7 @@ class GraphedRun:
     place (its version moved) is re-concatenated / re-transposed into them before the next replay."""
 
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, warmup=2,
-                 softmax_shift=None):
+                 softmax_shift=None, gather_dtype=None):
         if graph.device.type != "cuda":
             raise RuntimeError("GraphedRun captures device launches: the graph must be on a HIP device")
         self.tensors = tensors
@@ -1940,7 +1987,8 @@ class GraphedRun:
         side.wait_stream(torch.cuda.current_stream(graph.device))
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
-                Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift).run()
+                Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
+                         gather_dtype=gather_dtype).run()
         torch.cuda.current_stream(graph.device).wait_stream(side)
         torch.cuda.synchronize(graph.device)
         self.cuda_graph = torch.cuda.CUDAGraph()
@@ -1949,7 +1997,7 @@ class GraphedRun:
         try:
             with torch.cuda.graph(self.cuda_graph):
                 self.executor = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk,
-                                         softmax_shift=softmax_shift)
+                                         softmax_shift=softmax_shift, gather_dtype=gather_dtype)
                 self.outputs = self.executor.run()
         finally:
             taken, ops._CAPTURED_WT[:] = list(ops._CAPTURED_WT), []

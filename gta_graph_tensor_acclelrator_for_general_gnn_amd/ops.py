@@ -386,7 +386,7 @@ class BlockedPlan:
         fh, vq = F // heads, F // 16
         return fh % vq == 0 and 16 % (fh // vq) == 0
 
-    DTYPES = (torch.float32,)  # gathered-table dtypes of the blocked kernels
+    DTYPES = (torch.float32, torch.bfloat16)  # gathered-table dtypes of the blocked kernels
 
     @staticmethod
     def auto_blocks(graph, F, elem=4):
@@ -402,9 +402,9 @@ class BlockedPlan:
 
     @staticmethod
     def supports(F, heads, dtype=torch.float32):
-        """Shapes libgta's blocked kernels take: an fp32 table, F in {64, 128, 256} and, with head
-        weights, the quarter-wave form's lanes per head (F/heads)/(F/16) in {1, 2, 4, 8, 16} or the
-        one-item-per-wave form's (F/heads)/(F/64) in {4, 8, 16}."""
+        """Shapes libgta's blocked kernels take: an fp32 or bf16 table, F in {64, 128, 256} and, with
+        head weights, the quarter-wave form's lanes per head (F/heads)/(F/16) in {1, 2, 4, 8, 16} or
+        (fp32 tables only) the one-item-per-wave form's (F/heads)/(F/64) in {4, 8, 16}."""
         if dtype not in BlockedPlan.DTYPES or F not in (64, 128, 256):
             return False
         if not heads:
@@ -413,7 +413,7 @@ class BlockedPlan:
             return False
         fh, vq, vw = F // heads, F // 16, F // 64
         quarter = fh % vq == 0 and (fh // vq) in (1, 2, 4, 8, 16)
-        single = fh % vw == 0 and (fh // vw) in (4, 8, 16)
+        single = dtype == torch.float32 and fh % vw == 0 and (fh // vw) in (4, 8, 16)
         return quarter or single
 
 
@@ -421,10 +421,17 @@ def aggregate_blocked(graph, x, w=None, row_scale=None, out=None, accumulate=Fal
                       single_launch=True):
     """Same result as aggregate(graph, x, "src", w, ...) computed column block by column block so the
     gathered X slice stays L2-resident.  single_launch: one launch over (block, row) items into per-block
-    slabs + an ordered reduce; otherwise B dependent launches accumulating into out."""
+    slabs + an ordered reduce; otherwise B dependent launches accumulating into out.
+    x: fp32, or bf16 (gta_aggregate_blocked_x: rows widened exactly, every sum in fp32 -- bitwise the
+    call on x.float(); needs 16-B aligned rows, ldx % 8 == 0, as node_table / pitched make them)."""
     _need_gpu(x, w, row_scale, out, graph.indptr)
     F = x.shape[1]
-    ldx = _rows(x, "x")
+    if x.dtype not in BlockedPlan.DTYPES:
+        raise ValueError(f"aggregate_blocked: unsupported dtype={x.dtype}")
+    bf = x.dtype == torch.bfloat16
+    ldx = _rows(x, "x", x.dtype)
+    if bf and (ldx % 8 or x.data_ptr() % 16):
+        raise ValueError("aggregate_blocked: a bf16 x needs 16-B aligned rows (ldx % 8 == 0)")
     if x.shape[0] < graph.n_cols:
         raise ValueError("x must have n_cols rows")
     ldw, heads = 0, 0
@@ -443,6 +450,13 @@ def aggregate_blocked(graph, x, w=None, row_scale=None, out=None, accumulate=Fal
         out = (torch.zeros if accumulate else torch.empty)(graph.n_rows, F, dtype=torch.float32, device=x.device)
     ldy = _rows(out, "out")
     ws = plan.workspace(F) if single_launch else None
+    if bf:
+        check(_L().gta_aggregate_blocked_x(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols,
+                                           graph.nnz, _ptr(x), ldx, F, _lib.GTA_BF16, _ptr(w), ldw, heads,
+                                           _ptr(row_scale), _ptr(out), ldy, int(bool(accumulate)), _ptr(plan.buf),
+                                           plan.blocks, plan.item_edges, _ptr(ws), _stream(x.device)),
+              "aggregate_blocked_x")
+        return out
     check(_L().gta_aggregate_blocked(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols, graph.nnz,
                                      _ptr(x), ldx, F, _ptr(w), ldw, heads, _ptr(row_scale), _ptr(out), ldy,
                                      int(bool(accumulate)), _ptr(plan.buf), plan.blocks, plan.item_edges, _ptr(ws),
@@ -468,7 +482,9 @@ def gat_aggregate_blocked(graph, x, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize
     sf_out: an SF applied to out as it is written (GAT op 13; None = none), bitwise equal to
     apply_node(None, sf_out, out).  sums[i, h] = sum_e v (want_sums / sums given).  Returns (out, sums).
     shift: None, or the row-max table of softmax_shift for the same graph, scores and sf: the
-    overflow-safe form (gta_gat_aggregate_blocked_shifted), v = exp(g(a + b) - shift[dst])."""
+    overflow-safe form (gta_gat_aggregate_blocked_shifted), v = exp(g(a + b) - shift[dst]).
+    x: fp32, or bf16 (gta_gat_aggregate_blocked_x, shifted or not: bitwise the call on x.float();
+    16-B aligned rows, ldx % 8 == 0); the score tables, out and sums stay fp32."""
     _need_gpu(x, a_dst, b_src, out, sums, shift, graph.indptr)
     F, H = x.shape[1], a_dst.shape[1]
     if b_src.shape[1] != H:
@@ -488,6 +504,18 @@ def gat_aggregate_blocked(graph, x, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize
     if sums is not None and (not sums.is_contiguous() or tuple(sums.shape) != (graph.n_rows, H)):
         raise ValueError("gat_aggregate_blocked: sums must be a contiguous [N, heads] tensor")
     ws = plan.workspace_att(F, H)
+    if x.dtype == torch.bfloat16:
+        ldx = _rows(x, "x", torch.bfloat16)
+        if ldx % 8 or x.data_ptr() % 16:
+            raise ValueError("gat_aggregate_blocked: a bf16 x needs 16-B aligned rows (ldx % 8 == 0)")
+        if shift is not None:
+            _shift_table(graph, shift, H, "gat_aggregate_blocked")
+        check(_L().gta_gat_aggregate_blocked_x(
+            _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols, graph.nnz, _ptr(x), ldx, F,
+            _lib.GTA_BF16, _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"), H, _sf(sf),
+            1 if normalize else 0, _sf(sf_out), _ptr(out), _rows(out, "out"), _ptr(sums), _ptr(plan.buf), plan.blocks,
+            plan.item_edges, _ptr(ws), _ptr(shift), _stream(x.device)), "gat_aggregate_blocked_x")
+        return out, sums
     if shift is not None:
         _shift_table(graph, shift, H, "gat_aggregate_blocked")
         check(_L().gta_gat_aggregate_blocked_shifted(

@@ -8,6 +8,8 @@
 Each stage is pinned byte-exactly to the reference's own outputs (tests/test_frontend.py,
 test_compiler.py, test_lowering.py); the executor to the fp64 oracle (test_gpu_executor.py).
 """
+import torch
+
 from . import compiler, executor, frontend, ir, lowering, tiles
 from .semantics import Semantics
 
@@ -17,13 +19,18 @@ class Layer:
 
     def __init__(self, network, layer, graph, feature, reorder=False, heads=16, candidate=0, tile_start=None,
                  op_array=None, tile_size_list=None, metadata=None, pingpang=True, sinput=False, aggregator="ADD",
-                 stable_softmax=False):
+                 stable_softmax=False, gather_dtype=None):
         """pingpang / sinput: compile()'s isPingpang / isSinput (code/compiler.py:475-510) for the
         fusion search; the reference's start.py passes its command-line flags through.
         aggregator: the message gathers' reduce function, "ADD" / "MAX" / "MIN" / "MEAN"
         (frontend.gen_ops; the gathers' COMP_TYPE, executed by gta_reduce / the scaled aggregate).
         stable_softmax: run() evaluates the layer's softmax chains overflow-safe, exp(s - row max)
-        (Executor.softmax_shift); off, the default, is the unshifted path."""
+        (Executor.softmax_shift); off, the default, is the unshifted path.
+        gather_dtype: None (the default: nothing changes) or torch.bfloat16 -- run() stores the node
+        tables its column-blocked aggregates gather as bf16 (Executor.gather_dtype)."""
+        if gather_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError(f"gather_dtype: None, torch.float32 or torch.bfloat16, not {gather_dtype}")
+        self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
         self.network, self.layer, self.reorder = network, layer, reorder
         self.aggregator = aggregator
         self.stable_softmax = bool(stable_softmax)
@@ -74,11 +81,13 @@ class Layer:
     def run(self, tensors, plan_chunk=512, model=None, sync=True):
         """sync=False: no device synchronisation around the stream (res.elapsed_s is then host time
         only); a multi-layer forward synchronises once at its end instead of twice per layer."""
+        opts = {}  # only what is switched on: the default call is the one it always was
         if self.stable_softmax:
-            res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync,
-                                          softmax_shift=True)
-        else:
-            res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync)
+            opts["softmax_shift"] = True
+        if self.gather_dtype is not None:
+            opts["gather_dtype"] = self.gather_dtype
+        res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync,
+                                      **opts)
         if model:
             executor.attach_model(res, self.stream_records, self.tile_size_list, self.graph, model)
         return res, ex

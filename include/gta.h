@@ -51,7 +51,9 @@ extern "C" {
                               gta_build_id, gta_synth_alpha and gta_row_ids (scan-free setup); 13: gta_apply_edge_flat;
                               14: gta_aggregate_expr; 15: gta_reduce (gather MAX / MIN);
                               15 (additive): shifted softmax (gta_softmax_shift, gta_edge_softmax_shifted,
-                              gta_gat_aggregate_blocked_shifted; no existing signature changes) */
+                              gta_gat_aggregate_blocked_shifted; no existing signature changes);
+                              15 (additive): bf16 gathered tables in the blocked forms (gta_aggregate_blocked_x,
+                              gta_gat_aggregate_blocked_x; no existing signature changes) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -302,6 +304,36 @@ int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int
                               const float* b_src, int64_t ldb, int64_t heads, int sf, int normalize, int sf_out,
                               float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks, int64_t item_edges,
                               void* workspace, void* stream);
+
+/* ---- bf16 gathered tables in the blocked forms, ABI 15 additive -----------
+ * The two blocked aggregates with the gathered table's element type as an argument: x_dtype
+ * GTA_F32 (x is const float*; the call IS gta_aggregate_blocked / gta_gat_aggregate_blocked, or
+ * gta_gat_aggregate_blocked_shifted when shift != NULL) or GTA_BF16 (x holds bf16 rows, ldx in
+ * bf16 elements); any other x_dtype is GTA_ERR_ARG.  Everything else -- w, row_scale, the score
+ * tables a_dst / b_src, shift, y, sums, the slabs -- stays fp32; plans and workspaces are those of
+ * the fp32 calls (the size functions are shared).
+ * bf16 arithmetic: every gathered element widens to fp32 exactly (bits << 16: NaN, +-inf, -0 and
+ * bf16 denormals keep their value) and enters the fp32 kernel's chain -- fmaf(w, x, acc), or
+ * acc + x unweighted, per column in the item's edge order, the same per-head sums of v -- so a
+ * GTA_BF16 call is BITWISE EQUAL to the GTA_F32 call on the widened table with the same plan,
+ * blocks, item_edges and knobs.
+ * bf16 alignment: x 16-B aligned and ldx % 8 == 0 (rows of 16-B pieces).  Only the multi-item forms
+ * have a bf16 twin: a misaligned table, or head weights that do not fit them (F / heads not a
+ * multiple of F / 16, or lanes per head not dividing 16), return GTA_ERR_UNSUPPORTED where the
+ * fp32 call would fall back to one item per wave.  The 32-bit row addressing of the F = 128 forms
+ * needs n_cols < 2^24 and n_cols * ldx * 2 < 2^32 (larger tables take the 64-bit form).
+ * shift (gta_gat_aggregate_blocked_x): NULL = unshifted; else the table of gta_softmax_shift and
+ * the shifted form's restriction on sf (GTA_SF_EXP_LEAKY_RELU or GTA_SF_EXP, else
+ * GTA_ERR_UNSUPPORTED), for either x_dtype. */
+int gta_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                            const void* x, int64_t ldx, int64_t F, int x_dtype, const float* w, int64_t ldw,
+                            int64_t heads, const float* row_scale, float* y, int64_t ldy, int accumulate,
+                            const void* plan, int64_t blocks, int64_t item_edges, void* workspace, void* stream);
+int gta_gat_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                                int64_t nnz, const void* x, int64_t ldx, int64_t F, int x_dtype, const float* a_dst,
+                                int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf, int normalize,
+                                int sf_out, float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks,
+                                int64_t item_edges, void* workspace, const float* shift, void* stream);
 
 /* ---- CSC view of the CSR (ABI 11) -----------------------------------------
  * The edges ordered by SOURCE column, for the ISA gather / scatter with DIRECTION src

@@ -11,13 +11,15 @@ sys.path.insert(0, ROOT)
 from gta_graph_tensor_acclelrator_for_general_gnn_amd import configs, executor  # noqa: E402
 
 
-def main(names=None, reps=5, trace=False, graphed=False):
+def main(names=None, reps=5, trace=False, graphed=False, gather_dtype=None):
     dev = torch.device("cuda:0")
     out = {}
     for name in (names or list(configs.CONFIGS)):
         t0 = time.perf_counter()
         layers, g, tensors = configs.build(name, dev)
         build_s = time.perf_counter() - t0
+        for lay in layers:  # --gather-dtype bf16: the blocked aggregates' tables stored as bf16 (Layer.gather_dtype)
+            lay.gather_dtype = gather_dtype
         times = []
         nrep = reps if g.nnz > 10 ** 6 else 10 * reps  # small graphs: launch-bound, more samples
         for r in range(nrep + 1):
@@ -39,7 +41,7 @@ def main(names=None, reps=5, trace=False, graphed=False):
             for lay, t in zip(layers, tensors):
                 if prev is not None:
                     t["x"] = prev  # layer k reads layer k-1's (static) graph output
-                runs.append(executor.GraphedRun(lay.opgraph, lay.stream, g, t, lay.sem))
+                runs.append(executor.GraphedRun(lay.opgraph, lay.stream, g, t, lay.sem, gather_dtype=gather_dtype))
                 prev = runs[-1].outputs[sorted(runs[-1].outputs)[-1]]
             gt = []
             for r in range(reps + 1):
@@ -58,7 +60,8 @@ def main(names=None, reps=5, trace=False, graphed=False):
             for lay, t in zip(layers, tensors):
                 if x is not None:
                     t["x"] = x
-                res, ex = executor.run_stream(lay.opgraph, lay.stream, g, t, lay.sem, trace=True)
+                res, ex = executor.run_stream(lay.opgraph, lay.stream, g, t, lay.sem, trace=True,
+                                              gather_dtype=gather_dtype)
                 events += ex.trace_events
                 x = res.outputs[sorted(res.outputs)[-1]]
             executor.save_chrome_trace(events, os.path.join(ROOT, "gpurun_out", f"trace_{name}.json"))
@@ -89,8 +92,13 @@ if __name__ == "__main__":
         executor.AUTO_GRAPH_MAX_EDGES = 1 << 40
     if "--no-mlp" in sys.argv[1:]:  # the GIN MLP as two UPDATE launches (A/B of the fused chain)
         executor.FUSE_MLP = False
+    gdt = None
+    if "--gather-dtype" in argv:  # f32 (as they are) or bf16: Executor.gather_dtype for every layer
+        i = argv.index("--gather-dtype")
+        gdt = {"f32": None, "bf16": torch.bfloat16}[argv[i + 1]]
+        del argv[i:i + 2]
     if "--mm-rows-min" in argv:  # ops.MM_ROWS_MIN_M: smallest M for the row-streaming UPDATE entry
         i = argv.index("--mm-rows-min")
         ops.MM_ROWS_MIN_M = int(argv[i + 1])
         del argv[i:i + 2]
-    main(argv or None, trace="--trace" in sys.argv[1:], graphed="--hipgraph" in sys.argv[1:])
+    main(argv or None, trace="--trace" in sys.argv[1:], graphed="--hipgraph" in sys.argv[1:], gather_dtype=gdt)
