@@ -61,6 +61,8 @@ SIGNATURES = {
                                                  _vp]),
     "gta_aggregate_blocked_x": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp,
                                        _i64, _i32, _vp, _i64, _i64, _vp, _vp]),
+    "gta_reduce_blocked": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64,
+                                  _vp, _vp]),
     "gta_gat_aggregate_blocked_x": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64,
                                            _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "gta_apply_edge_flat": (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _vp, _i64,

@@ -1316,6 +1316,184 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   }
 }
 
+// ---------------------------------------------------------------------------
+// Column-blocked MAX / MIN (gta_reduce_blocked): the unweighted item kernels with gta_reduce's
+// reducer in place of the add.  A max cannot ride on the sum's `valid ? t : 0`, so these are
+// kernels of their own: accumulators start at the identity -inf, every value is flipped by the
+// wave-uniform sign bit on its way in (MIN = -max(-x), exact, one instantiation for both) and an
+// idle edge slot holds the identity -- as a bit pattern that the flip turns into -inf
+// (red_idle), so the fold needs no per-edge select and masked lanes issue no loads.  Item k's
+// slab row holds its partial in the MAX domain; k_seg_reduce_red folds and flips back.  An item
+// without edges, or a lane group past n_items, stores nothing.
+// ---------------------------------------------------------------------------
+template <bool BF> struct RedIdle {  // the row piece whose every element flips to -inf
+  static __device__ __forceinline__ float4 make(uint32_t sbit) {
+    const float v = __uint_as_float(0xff800000u ^ sbit);
+    return make_float4(v, v, v, v);
+  }
+};
+template <> struct RedIdle<true> {
+  static __device__ __forceinline__ uint2 make(uint32_t sbit) {
+    const uint32_t h = (0xff800000u ^ sbit) >> 16, v = h | (h << 16);
+    return make_uint2(v, v);
+  }
+};
+
+// k_agg_seg4's unweighted form (same item decode, index broadcast, Row4<BF> loads and lanes):
+// G = 16 for F = 64 / 256 (four items per wave), G = 32 for F = 128 (two; non-temporal slab stores)
+template <int VW, int U, int G, bool BF>
+__global__ void __launch_bounds__(kBlock)
+k_red_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
+           int64_t ldx, uint32_t sbit, float* __restrict__ slabs, const SegItem* __restrict__ items) {
+  constexpr int F = G * VW;
+  constexpr int IPW = kWave / G;  // items per wave
+  constexpr int NQ = VW / 4;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int l16 = lane & (G - 1);
+  const int64_t k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * IPW + lane / G;
+  const int64_t n_items = *n_items_p;
+  SegItem it{0, 0, 0};
+  if (k < n_items) it = items[k];
+  const int len = it.len;
+  int mx = len;
+#pragma unroll
+  for (int off = G; off < kWave; off <<= 1) mx = max(mx, __shfl_xor(mx, off));
+  const int maxlen = __builtin_amdgcn_readfirstlane(mx);
+  if (maxlen == 0) return;
+  const int64_t eb = it.beg;
+  const int col = l16 * VW;
+  const typename Row4<BF>::type idle = RedIdle<BF>::make(sbit);
+  float acc[VW];
+#pragma unroll
+  for (int q = 0; q < VW; ++q) acc[q] = -__builtin_inff();
+  int idxv = (l16 < len) ? indices[eb + l16] : 0;
+  for (int c = 0; c < maxlen; c += G) {
+    const int idxn = (c + G + l16 < len) ? indices[eb + c + G + l16] : 0;
+#pragma unroll
+    for (int s = 0; s < G; s += U) {
+      if (c + s >= maxlen) break;
+      typename Row4<BF>::type xv[U][NQ];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int src = bcastG<G>(idxv, s + u);
+        if (c + s + u < len) {
+          if constexpr (BF) {  // the lane's VW bf16: one 8-B load (VW = 4) or 16-B loads (VW = 16)
+            const uint16_t* pb = reinterpret_cast<const uint16_t*>(x) + static_cast<int64_t>(src) * ldx + col;
+            if constexpr (NQ % 2 == 0) {
+#pragma unroll
+              for (int q = 0; q < NQ; q += 2) {
+                const uint4 t = reinterpret_cast<const uint4*>(pb)[q / 2];
+                xv[u][q] = make_uint2(t.x, t.y);
+                xv[u][q + 1] = make_uint2(t.z, t.w);
+              }
+            } else {
+#pragma unroll
+              for (int q = 0; q < NQ; ++q) xv[u][q] = reinterpret_cast<const uint2*>(pb)[q];
+            }
+          } else {
+            const float4* p = reinterpret_cast<const float4*>(x + static_cast<int64_t>(src) * ldx + col);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) xv[u][q] = p[q];
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) xv[u][q] = idle;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          const float4 xw = row4_f32(xv[u][q]);
+          const float* xf = reinterpret_cast<const float*>(&xw);
+#pragma unroll
+          for (int t = 0; t < 4; ++t) acc[4 * q + t] = red_max(acc[4 * q + t], red_flip(xf[t], sbit));
+        }
+      }
+    }
+    idxv = idxn;
+  }
+  if (len > 0) {
+    float* o = slabs + k * F + col;
+#pragma unroll
+    for (int q = 0; q < VW; ++q) {
+      if (G == 32) __builtin_nontemporal_store(acc[q], o + q);
+      else o[q] = acc[q];
+    }
+  }
+}
+
+// Lean F = 128 form, modelled on k_agg_h32<false, ...>: 32-bit row addressing (the host checks
+// n_cols < 2^24 and a table span < 2^32 bytes, in the table's own element size) and unmasked steps
+// where both items still hold 8 edges.  NT bit 0: non-temporal index loads, bit 1: slab stores.
+template <int NT, bool BF>
+__global__ void __launch_bounds__(kBlock)
+k_red_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
+          uint32_t row_bytes, uint32_t sbit, float* __restrict__ slabs, const SegItem* __restrict__ items) {
+  constexpr int G = 32, F = 128, U = 8;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int l32 = lane & (G - 1);
+  const int64_t k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * 2 + (lane >> 5);
+  const int64_t n_items = *n_items_p;
+  SegItem it{0, 0, 0};
+  if (k < n_items) it = items[k];
+  const int len = it.len;
+  const int other = __shfl_xor(len, 32);
+  const int maxlen = __builtin_amdgcn_readfirstlane(max(len, other));
+  const int minlen = __builtin_amdgcn_readfirstlane(min(len, other));
+  if (maxlen == 0) return;
+  typedef typename Row4<BF>::type XR;
+  const uint32_t colb = static_cast<uint32_t>(l32) * (BF ? 8u : 16u);
+  const char* xb = reinterpret_cast<const char*>(x);
+  const int32_t* ic = indices + it.beg;  // chunk cursor: advanced once per 32 edges
+  const XR idle = RedIdle<BF>::make(sbit);
+  const float ident = -__builtin_inff();
+  float acc[4] = {ident, ident, ident, ident};
+  auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
+  auto row = [&](int src) -> XR {
+    return *reinterpret_cast<const XR*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
+  };
+  int idxv = (l32 < len) ? ldi(ic + l32) : 0;
+  for (int c = 0; c < maxlen; c += G) {
+    const int idxn = (c + G + l32 < len) ? ldi(ic + G + l32) : 0;
+#pragma unroll
+    for (int s = 0; s < G; s += U) {
+      if (c + s >= maxlen) break;
+      XR xv[U];
+      if (c + s + U <= minlen) {  // full step for both items: no masks
+#pragma unroll
+        for (int u = 0; u < U; ++u) xv[u] = row(bcastG<G>(idxv, s + u));
+      } else {
+        const int rem = len - c - s;  // edges of this item left at this step (may be <= 0)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int src = bcastG<G>(idxv, s + u);
+          if (u < rem) xv[u] = row(src);
+          else xv[u] = idle;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float4 xw = row4_f32(xv[u]);
+        acc[0] = red_max(acc[0], red_flip(xw.x, sbit));
+        acc[1] = red_max(acc[1], red_flip(xw.y, sbit));
+        acc[2] = red_max(acc[2], red_flip(xw.z, sbit));
+        acc[3] = red_max(acc[3], red_flip(xw.w, sbit));
+      }
+    }
+    idxv = idxn;
+    ic += G;
+  }
+  if (len > 0) {
+    float* o = slabs + k * F + l32 * 4;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (NT & 2) __builtin_nontemporal_store(acc[t], o + t);
+      else o[t] = acc[t];
+    }
+  }
+}
+
 // Round 6: the metric kernel with its two streamed inputs -- alpha (32 B per edge) and the source
 // indices (4 B) -- pre-fetched into L2 by SCALAR loads (knob seg_pf; k_agg_h32<A1> otherwise).
 // Why: counters of k_agg_h32 (profiles/r05/wcost_pmc_summary.json) put the kernel's limit in the
@@ -1723,6 +1901,40 @@ k_seg_reduce(int64_t n_rows, const float* __restrict__ slabs, const float* __res
     for (int q = 0; q < VW; ++q) o.v[q] = scale * acc[q];
   }
   o.store(yp);
+}
+
+// k_seg_reduce for gta_reduce_blocked: the row's slab rows (partial maxima in the MAX domain,
+// k_red_seg4 / k_red_h32) folded with red_max and flipped back.  A row without items -- a row
+// without edges -- gets 0, decided from its item count, never from the identity.
+template <int VW>
+__global__ void __launch_bounds__(kBlock)
+k_seg_reduce_red(int64_t n_rows, const float* __restrict__ slabs, uint32_t sbit, float* __restrict__ y, int64_t ldy,
+                 RowItems ri) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  if (row >= n_rows) return;
+  const int col = lane * VW;
+  constexpr int F = kWave * VW;
+  const bool empty = ri.row_ptr[row] == ri.row_ptr[row + 1];
+  float acc[VW];
+#pragma unroll
+  for (int q = 0; q < VW; ++q) acc[q] = -__builtin_inff();
+  for_row_items<VW>(ri, row, lane, [&](int64_t i0, int64_t i1, int64_t i2, int64_t i3, int m) {
+    Vec<VW> p[4];
+    p[0].load(slabs + i0 * F + col);
+    if (m == 4) {
+      p[1].load(slabs + i1 * F + col);
+      p[2].load(slabs + i2 * F + col);
+      p[3].load(slabs + i3 * F + col);
+    }
+    for (int u = 0; u < m; ++u)
+#pragma unroll
+      for (int q = 0; q < VW; ++q) acc[q] = red_max(acc[q], p[u].v[q]);
+  });
+  Vec<VW> o;
+#pragma unroll
+  for (int q = 0; q < VW; ++q) o.v[q] = empty ? 0.f : red_flip(acc[q], sbit);
+  o.store(y + row * ldy + col);
 }
 
 // Ordered reduce of the attention form: y[row, c] = sf_out(sum_k acc_k / sum_k s_k[head(c)])
@@ -4980,6 +5192,83 @@ int gta_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, int64
                             const void* plan, int64_t blocks, int64_t item_edges, void* workspace, void* stream) {
   return aggregate_blocked_impl("aggregate_blocked_x", indptr, indices, n_rows, n_cols, nnz, x, ldx, F, x_dtype, w,
                                 ldw, heads, row_scale, y, ldy, accumulate, plan, blocks, item_edges, workspace, stream);
+}
+
+// gta_reduce_blocked: one argument check, one dispatch.  MAX / MIN launch the k_red_* twins of the
+// unweighted multi-item forms over the blocked plan's items, then k_seg_reduce_red; ADD is the
+// blocked aggregate itself.
+int gta_reduce_blocked(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                       int64_t nnz, const void* xv, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy,
+                       const void* plan, int64_t blocks, int64_t item_edges, void* workspace, void* stream) {
+  const std::string who = "reduce_blocked";
+  if (red != GTA_RED_ADD && red != GTA_RED_MAX && red != GTA_RED_MIN)
+    return fail(GTA_ERR_ARG, who + ": red must be GTA_RED_ADD, GTA_RED_MAX or GTA_RED_MIN");
+  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, who + ": x_dtype must be F32 or BF16");
+  if (n_rows < 0 || n_cols < 0 || nnz < 0 || F <= 0 || blocks < 1 || blocks > 63 || item_edges < 1)
+    return fail(GTA_ERR_ARG, who + ": bad sizes (1 <= blocks <= 63, item_edges >= 1)");
+  if (n_rows == 0) return GTA_OK;
+  if (!indptr || !y || !plan || ldy < F) return fail(GTA_ERR_ARG, who + ": bad arguments");
+  if (nnz > 0 && (!indices || !xv || !workspace || ldx < F))
+    return fail(GTA_ERR_ARG, who + ": indices, x (ldx >= F) and the slab workspace are needed when nnz > 0");
+  if (red == GTA_RED_ADD) {  // the sum is the blocked aggregate's: no weights, no row scale, no accumulate
+    if (nnz == 0) { xv = y; ldx = ldy; x_dtype = GTA_F32; }  // any valid address: there is no item to read it
+    const int rc = aggregate_blocked_impl(who + " (ADD)", indptr, indices, n_rows, n_cols, nnz, xv, ldx, F, x_dtype,
+                                          nullptr, 0, 0, nullptr, y, ldy, 0, plan, blocks, item_edges, workspace, stream);
+    return rc;
+  }
+  const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
+  const bool bf = x_dtype == GTA_BF16;
+  int vw = 0;
+  for (int c : {4, 2, 1})
+    if (F == static_cast<int64_t>(kWave) * c && ldy % c == 0 && aligned(y, 4 * c)) { vw = c; break; }
+  if (!vw) return fail(GTA_ERR_UNSUPPORTED, who + ": F must be 64, 128 or 256 with y rows aligned to F/64 floats");
+  if (nnz > 0 && (ldx % (bf ? 8 : 4) != 0 || !aligned(xv, 16)))  // multi-item forms only: no one-item-per-wave twin
+    return fail(GTA_ERR_UNSUPPORTED, who + ": x must be 16-B aligned with ldx % 4 == 0 (fp32) or ldx % 8 == 0 (bf16)");
+  const int B = static_cast<int>(blocks);
+  const int64_t items = blocked_max_items(n_rows, nnz, B, item_edges);  // grid bound; the kernels stop at n_items
+  BlockedView v = blocked_view(const_cast<void*>(plan), n_rows, B, items);
+  hipStream_t s = S(stream);
+  const RowItems ri{v.row_ptr, v.row_items};
+  float* slabs = static_cast<float*>(workspace);
+  const float* x = static_cast<const float*>(xv);  // bf: bf16 rows, read as such by the BF kernels only
+  const int64_t* nit = &v.hdr[4];
+  const SegItem* its = v.items;
+  const uint32_t sbit = red == GTA_RED_MIN ? 0x80000000u : 0u;
+  const unsigned xe = bf ? 2u : 4u;  // bytes per gathered element
+  const dim3 blk(kBlock);
+  if (items == 0) {
+    // no edges: no items; the reduce below writes the (empty) rows
+  } else if (F == 128) {  // half-wave items
+    const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
+    const bool lean = tuning().seg_lean && n_cols < (1 << 24) &&
+                      static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * xe < (1ull << 32);
+    if (lean) {
+      const uint32_t rb = static_cast<uint32_t>(ldx * xe);
+      if (bf) k_red_h32<2, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, sbit, slabs, its);
+      else k_red_h32<2, false><<<g2h, blk, 0, s>>>(indices, nit, x, rb, sbit, slabs, its);
+      GTA_LAUNCHED("k_red_h32");
+    } else {
+      if (bf) k_red_seg4<4, 8, 32, true><<<g2h, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
+      else k_red_seg4<4, 8, 32, false><<<g2h, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
+      GTA_LAUNCHED("k_red_seg4<half>");
+    }
+  } else {  // F = 64 / 256: quarter-wave items
+    const dim3 g4(static_cast<unsigned>((items + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock)));
+    if (F == 64) {
+      if (bf) k_red_seg4<4, 4, 16, true><<<g4, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
+      else k_red_seg4<4, 4, 16, false><<<g4, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
+    } else {
+      if (bf) k_red_seg4<16, 2, 16, true><<<g4, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
+      else k_red_seg4<16, 2, 16, false><<<g4, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
+    }
+    GTA_LAUNCHED("k_red_seg4");
+  }
+  const dim3 g3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
+  if (vw == 2) k_seg_reduce_red<2><<<g3, blk, 0, s>>>(n_rows, slabs, sbit, y, ldy, ri);
+  else if (vw == 4) k_seg_reduce_red<4><<<g3, blk, 0, s>>>(n_rows, slabs, sbit, y, ldy, ri);
+  else k_seg_reduce_red<1><<<g3, blk, 0, s>>>(n_rows, slabs, sbit, y, ldy, ri);
+  GTA_LAUNCHED("k_seg_reduce_red");
+  return GTA_OK;
 }
 
 int64_t gta_gat_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, int64_t blocks, int64_t F,

@@ -203,6 +203,10 @@ class Executor:
         # run column-blocked (L2-resident slices) when the shape allows it
         self.blocked_min_table_bytes = 32 << 20
         self.blocked_blocks = "auto"  # ops.BlockedPlan.auto_blocks, or a fixed count (0 = never)
+        #   reduce_blocked: a MAX / MIN gather of a source-gathered node table passes the same gate to
+        #   ops.reduce_blocked (values identical to ops.reduce's: every output is one of its inputs);
+        #   False keeps the row-chunked gta_reduce (A/B)
+        self.reduce_blocked = True
         self.consumers = {i: [] for i in range(len(opgraph))}
         for i in range(len(opgraph)):
             for src in opgraph.inputs[i]:
@@ -232,8 +236,10 @@ class Executor:
         #   bitwise the fp32 run on the rounded table (gta_aggregate_blocked_x).  A table that is bf16
         #   already (a bf16 model input) takes the blocked form by the same size rule, with no cast.
         #   One cast per table value, shared by its consumers (_gather_cast; gather_casts counts
-        #   them).  Left as they are: the row-chunked form (tables under the size gate), MAX / MIN /
-        #   expression gathers, self-term forms, ORDER C and distributed.py.
+        #   them).  The MAX / MIN gathers that pass the gate (_eval_reduce, reduce_blocked) take the
+        #   same cast table -- rounding commutes with the max -- and under this option only, MEAN runs
+        #   as the blocked aggregate with row_scale = 1 / deg.  Left as they are: the row-chunked form
+        #   (tables under the size gate), expression gathers, self-term forms, ORDER C and distributed.py.
         if gather_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError(f"gather_dtype: None, torch.float32 or torch.bfloat16, not {gather_dtype}")
         self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
@@ -1123,7 +1129,26 @@ class Executor:
             else:
                 t, g, mode = self._to_edge_tensor(v), self.graph, "edge"
                 nbytes = E * t.shape[1] * F4 + n_out * (8 + t.shape[1] * F4)
-        if op.comp == "MEAN":
+        # column-blocked when a source-gathered node table outgrows L2 (_spmm's gate, evaluated before
+        # any blocked op is named): ORDER R of a scatter C on the layer's CSR, ORDER C of a scatter R
+        # over the transposed view.  MAX / MIN values are identical by construction; MEAN moves only
+        # under gather_dtype bf16 (its blocked sum order would change the default bits)
+        B, view = 0, None
+        if self.reduce_blocked and isinstance(v, Scat):
+            on = self.gather_dtype == torch.bfloat16
+            if op.order != "C" and v.mode == "src" and (op.comp != "MEAN" or on):
+                B = self._blocked_blocks(t, "src", 0)
+            elif op.order == "C" and v.mode == "dst" and op.comp != "MEAN":
+                view = g
+                B = self._blocked_blocks(t, "src", 0, view)
+        if B:
+            tb = self._gather_cast(t) if view is None else t
+            nbytes = E * (4 + t.shape[1] * tb.element_size()) + n_out * (8 + t.shape[1] * F4)
+            if op.comp == "MEAN":
+                y = ops.aggregate_blocked(g, tb, None, row_scale=_mean_scale(g), blocks=B)
+            else:
+                y = ops.reduce_blocked(g, tb, op.comp, blocks=B)
+        elif op.comp == "MEAN":
             y = ops.aggregate(g, t, mode, None, row_scale=_mean_scale(g), plan=self._plan())
         else:
             y = ops.reduce(g, t, op.comp, mode, plan=self._plan())

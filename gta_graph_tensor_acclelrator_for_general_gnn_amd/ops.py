@@ -7,7 +7,9 @@ One function per ISA op / fused pattern of the GTA stream:
                (hardware_info.yaml Inst_fused :35-38, code/interpreter.py:575-636, 764-802) -> gta_aggregate
   reduce       ISA `gather` with COMP_TYPE MAX / MIN: rows without edges 0, NaN propagates, every
                output bitwise one of its inputs (+0 / -0 apart)             -> gta_reduce
-  apply_edge   applyedge ADD/MUL/SF (genGraphOP.py:36, 55-60)              -> gta_apply_edge
+  reduce_blocked  the same MAX / MIN gather of a node table, column-blocked for tables beyond L2
+               (the blocked aggregate's plan and slab rows)                 -> gta_reduce_blocked
+  apply_edge   applyedge ADD/MUL/SF (genGraphOP.py:36, 55-60)            -> gta_apply_edge
   aggregate_expr  a tree of applyedge ops -> gather ADD, fused (DGN, PNA)   -> gta_aggregate_expr
   apply_node   applynode ADD/MUL/SF (genGraphOP.py:62, 94-95, 103-108)     -> gta_apply_node
   update_mm    applynode/applyedge MM, `j,ij->i` (ISA_defination.yaml:1-31) -> gta_update_mm
@@ -461,6 +463,46 @@ def aggregate_blocked(graph, x, w=None, row_scale=None, out=None, accumulate=Fal
                                      _ptr(x), ldx, F, _ptr(w), ldw, heads, _ptr(row_scale), _ptr(out), ldy,
                                      int(bool(accumulate)), _ptr(plan.buf), plan.blocks, plan.item_edges, _ptr(ws),
                                      _stream(x.device)), "aggregate_blocked")
+    return out
+
+
+def reduce_blocked(graph, x, red="MAX", out=None, plan=None, blocks=32):
+    """Same result as reduce(graph, x, red, "src") computed column block by column block
+    (gta_reduce_blocked), for a gathered table beyond L2: the blocked plan's items write partial
+    maxima to the slab rows and an ordered pass folds each row's.  reduce's rules hold (rows without
+    edges 0, NaN propagates, every output bitwise one of its inputs, +0 / -0 apart), so the value
+    does not depend on plan, blocks or item length.  "ADD" is aggregate_blocked(graph, x, None).
+    x: fp32 (16-B aligned rows, ldx % 4 == 0), or bf16 (widened exactly; ldx % 8 == 0); F in
+    {64, 128, 256}; y float32.  graph may be a CSC.view("dst"): the reduce to the SOURCE nodes."""
+    _need_gpu(x, out, graph.indptr)
+    if red not in _REDS:
+        raise ValueError(f"reduce_blocked: red must be one of {sorted(_REDS)} (got {red!r})")
+    if x.dtype not in BlockedPlan.DTYPES:
+        raise ValueError(f"reduce_blocked: unsupported dtype={x.dtype}")
+    F = x.shape[1]
+    if not BlockedPlan.supports(F, 0, x.dtype):
+        raise ValueError(f"reduce_blocked: unsupported F={F}, dtype={x.dtype}")
+    bf = x.dtype == torch.bfloat16
+    ldx = _rows(x, "x", x.dtype)
+    if ldx % (8 if bf else 4) or x.data_ptr() % 16:
+        raise ValueError("reduce_blocked: x needs 16-B aligned rows (ldx % 4 == 0 for fp32, ldx % 8 == 0 for bf16)")
+    if x.shape[0] < graph.n_cols:
+        raise ValueError("x must have n_cols rows")
+    if plan is None:
+        plan = graph.blocked_plan(blocks)
+    if not plan.sorted:
+        raise ValueError("reduce_blocked needs every CSR row's columns sorted")
+    if out is None:
+        out = torch.empty(graph.n_rows, F, dtype=torch.float32, device=x.device)
+    ldy = _rows(out, "out")
+    if out.shape[0] < graph.n_rows or out.shape[1] != F:
+        raise ValueError("out must be [N, F]")
+    if graph.n_rows == 0:
+        return out
+    check(_L().gta_reduce_blocked(_REDS[red], _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols,
+                                  graph.nnz, _ptr(x), ldx, F, _lib.GTA_BF16 if bf else _lib.GTA_F32, _ptr(out), ldy,
+                                  _ptr(plan.buf), plan.blocks, plan.item_edges, _ptr(plan.workspace(F)),
+                                  _stream(x.device)), "reduce_blocked")
     return out
 
 

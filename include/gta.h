@@ -53,7 +53,8 @@ extern "C" {
                               15 (additive): shifted softmax (gta_softmax_shift, gta_edge_softmax_shifted,
                               gta_gat_aggregate_blocked_shifted; no existing signature changes);
                               15 (additive): bf16 gathered tables in the blocked forms (gta_aggregate_blocked_x,
-                              gta_gat_aggregate_blocked_x; no existing signature changes) */
+                              gta_gat_aggregate_blocked_x; no existing signature changes);
+                              15 (additive): gta_reduce_blocked (column-blocked gather MAX / MIN) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -334,6 +335,31 @@ int gta_gat_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, i
                                 int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf, int normalize,
                                 int sf_out, float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks,
                                 int64_t item_edges, void* workspace, const float* shift, void* stream);
+
+/* ---- K2' column-blocked REDUCE (gather MAX / MIN of a table beyond L2), ABI 15 additive ----
+ * The same y as gta_reduce(red, ..., GTA_IDX_SRC, x, ...), computed over the column blocks of
+ * gta_aggregate_blocked: the plan is gta_aggregate_blocked_plan_build's and the workspace
+ * gta_aggregate_blocked_workspace_bytes' (the same items, the same [items, F] fp32 slab rows; rows'
+ * columns sorted).  Item k writes its partial maximum to slab row k and a second kernel folds each
+ * row's slab rows.  gta_reduce's rules hold:
+ *  - a row without edges gets 0.0f, decided from the row having no items, never from the identity;
+ *  - NaN propagates; a row whose every value is -inf gives -inf under MAX (+inf under MIN likewise);
+ *  - which of +0 / -0 is returned is unspecified; apart from that every output element is bitwise
+ *    one of its inputs, so y equals gta_reduce's for any plan, blocks, item_edges and kernel form.
+ * red GTA_RED_ADD is gta_aggregate_blocked_x with w NULL, no row_scale, no accumulate.
+ * x_dtype GTA_F32 or GTA_BF16 (rows widened exactly, bits << 16; ldx in bf16 elements; RNE rounding
+ * to bf16 is monotone, so the max of the rounded rows is the rounding of the max); y is fp32.  No
+ * weights, row_scale or accumulate.
+ * Shapes (MAX / MIN): F in {64, 128, 256} on the multi-item forms only -- fp32 x 16-B aligned with
+ * ldx % 4 == 0, bf16 x 16-B aligned with ldx % 8 == 0, y rows aligned to F / 64 floats as in
+ * gta_aggregate_blocked; anything else GTA_ERR_UNSUPPORTED (there is no one-item-per-wave twin).
+ * F = 128 takes the 32-bit row addressing under gta_aggregate_blocked_x's guards (knob seg_lean).
+ * GTA_ERR_ARG, before any memory is touched: a bad red or x_dtype, blocks outside 1..63,
+ * item_edges < 1, NULL indptr / y / plan, NULL x / indices / workspace with nnz > 0.
+ * n_rows == 0 returns GTA_OK; nnz == 0: y all zero, x and indices never read. */
+int gta_reduce_blocked(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                       int64_t nnz, const void* x, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy,
+                       const void* plan, int64_t blocks, int64_t item_edges, void* workspace, void* stream);
 
 /* ---- CSC view of the CSR (ABI 11) -----------------------------------------
  * The edges ordered by SOURCE column, for the ISA gather / scatter with DIRECTION src
