@@ -1046,6 +1046,173 @@ __device__ __forceinline__ float4 row4_f32(const uint2& r) {
                      __uint_as_float(r.y & 0xffff0000u));
 }
 
+// ---- what the blocked item kernels share: item decode, row loads, slab-row store, the fold ----
+
+// The wave's items: G lanes each (16: four per wave, 32: two), lane group j takes item
+// (wave id) * (64 / G) + j; a group past n_items holds an empty item.  maxlen is the wave's longest
+// item (wave-uniform), minlen (G = 32 only, where it is one more min on the same exchanged length)
+// the shorter of its two.  One function for both widths: at G = 32 the butterfly is the single
+// __shfl_xor the half-wave kernels always had, and a caller that does not read minlen drops it.
+struct ItemSlot {
+  int64_t k;  // item id = slab row
+  SegItem it;
+  int maxlen, minlen;
+};
+template <int G>
+__device__ __forceinline__ ItemSlot item_decode(const int64_t* n_items_p, const SegItem* items,
+                                                int lane) {
+  ItemSlot d;
+  d.k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * (kWave / G) + lane / G;
+  const int64_t n_items = *n_items_p;
+  d.it = SegItem{0, 0, 0};
+  if (d.k < n_items) d.it = items[d.k];
+  const int len = d.it.len;
+  if constexpr (G == 32) {
+    const int other = __shfl_xor(len, 32);
+    d.maxlen = __builtin_amdgcn_readfirstlane(max(len, other));
+    d.minlen = __builtin_amdgcn_readfirstlane(min(len, other));
+  } else {
+    int mx = len;
+#pragma unroll
+    for (int off = G; off < kWave; off <<= 1) mx = max(mx, __shfl_xor(mx, off));
+    d.maxlen = __builtin_amdgcn_readfirstlane(mx);
+    d.minlen = 0;
+  }
+  return d;
+}
+
+// Lean addressing (the half-wave kernels): row src of a table as the uniform base plus a 32-bit
+// byte offset src * row_bytes + off (v_mul_u32_u24; the host checks lean32_ok), so the load takes
+// the SGPR-base + VGPR-offset form.  T: the lane's piece, Row4<BF>::type of an x row or one score.
+template <class T>
+__device__ __forceinline__ T lean_at(const char* base, int src, uint32_t row_bytes, uint32_t off) {
+  return *reinterpret_cast<const T*>(base + (__umul24(static_cast<uint32_t>(src), row_bytes) + off));
+}
+
+// Generic addressing (64-bit): the lane's NQ pieces of row src from column col.  bf16: one 8-B load
+// (NQ = 1) or 16-B loads split into two pieces each (NQ = 4).
+template <bool BF, int NQ>
+__device__ __forceinline__ void row_load(const float* x, int64_t ldx, int src, int col,
+                                         typename Row4<BF>::type (&xv)[NQ]) {
+  if constexpr (BF) {
+    const uint16_t* pb = reinterpret_cast<const uint16_t*>(x) + static_cast<int64_t>(src) * ldx + col;
+    if constexpr (NQ % 2 == 0) {
+#pragma unroll
+      for (int q = 0; q < NQ; q += 2) {
+        const uint4 t = reinterpret_cast<const uint4*>(pb)[q / 2];
+        xv[q] = make_uint2(t.x, t.y);
+        xv[q + 1] = make_uint2(t.z, t.w);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) xv[q] = reinterpret_cast<const uint2*>(pb)[q];
+    }
+  } else {
+    const float4* p = reinterpret_cast<const float4*>(x + static_cast<int64_t>(src) * ldx + col);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) xv[q] = p[q];
+  }
+}
+
+// The lane's VW partials to its slab row (NTS: non-temporal, the row is read once by the reduce)
+template <bool NTS, int VW>
+__device__ __forceinline__ void slab_store(float* o, const float (&acc)[VW]) {
+#pragma unroll
+  for (int q = 0; q < VW; ++q) {
+    if (NTS) __builtin_nontemporal_store(acc[q], o + q);
+    else o[q] = acc[q];
+  }
+}
+
+// The fold of the unweighted item walks and of the ordered reduce: the accumulator's start value,
+// the row piece an idle edge slot holds, and the per-element combine.
+// FoldSum: 0, zeros, acc + x.
+// FoldMax (gta_reduce_blocked's MAX / MIN): a max cannot ride on the sum's `valid ? t : 0`, so the
+// accumulators start at the identity -inf, every value is flipped by the wave-uniform sign bit on
+// its way in (MIN = -max(-x), exact, one instantiation for both) and an idle slot holds the
+// identity -- as the bit pattern that the flip turns into -inf (RedIdle), so the fold needs no
+// per-edge select and masked lanes issue no loads.  Slab rows hold partials in the MAX domain: the
+// ordered reduce folds them with sbit 0 and flips the result back.
+template <bool BF> struct RedIdle {  // the row piece whose every element flips to -inf
+  static __device__ __forceinline__ float4 make(uint32_t sbit) {
+    const float v = __uint_as_float(0xff800000u ^ sbit);
+    return make_float4(v, v, v, v);
+  }
+};
+template <> struct RedIdle<true> {
+  static __device__ __forceinline__ uint2 make(uint32_t sbit) {
+    const uint32_t h = (0xff800000u ^ sbit) >> 16, v = h | (h << 16);
+    return make_uint2(v, v);
+  }
+};
+template <bool BF> struct FoldSum {
+  static constexpr float kInit = 0.f;
+  __device__ __forceinline__ typename Row4<BF>::type idle() const { return Row4<BF>::zero(); }
+  __device__ __forceinline__ float combine(float acc, float x) const { return acc + x; }
+};
+template <bool BF> struct FoldMax {
+  uint32_t sbit;
+  static constexpr float kInit = -__builtin_inff();
+  __device__ __forceinline__ typename Row4<BF>::type idle() const { return RedIdle<BF>::make(sbit); }
+  __device__ __forceinline__ float combine(float acc, float x) const { return red_max(acc, red_flip(x, sbit)); }
+};
+
+// The unweighted walk of a G-lane item (k_agg_seg4 without weights, k_red_seg4): a chunk's G source
+// indices arrive in one coalesced load (the next chunk's behind it) and are broadcast lane by lane;
+// per step U rows are gathered, lanes of a finished item masked off, and folded.  An item without
+// edges, or a lane group past n_items, stores nothing.  NT as in k_agg_seg4.
+template <int VW, int U, int G, int NT, bool BF, class Fold>
+__device__ __forceinline__ void seg4_walk(const int32_t* indices, const int64_t* n_items_p,
+                                          const float* x, int64_t ldx, float* slabs,
+                                          const SegItem* items, Fold fold) {
+  constexpr int F = G * VW;
+  constexpr int NQ = VW / 4;
+  typedef typename Row4<BF>::type XR;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int l16 = lane & (G - 1);
+  const ItemSlot d = item_decode<G>(n_items_p, items, lane);
+  const int len = d.it.len, maxlen = d.maxlen;
+  if (maxlen == 0) return;
+  const int64_t eb = d.it.beg;
+  const int col = l16 * VW;
+  const XR idle = fold.idle();
+  float acc[VW];
+#pragma unroll
+  for (int q = 0; q < VW; ++q) acc[q] = Fold::kInit;
+  auto ldi = [&](int64_t e) { return (NT & 1) ? __builtin_nontemporal_load(indices + e) : indices[e]; };
+  int idxv = (l16 < len) ? ldi(eb + l16) : 0;
+  for (int c = 0; c < maxlen; c += G) {
+    const int idxn = (c + G + l16 < len) ? ldi(eb + c + G + l16) : 0;
+#pragma unroll
+    for (int s = 0; s < G; s += U) {
+      if (c + s >= maxlen) break;
+      XR xv[U][NQ];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int src = bcastG<G>(idxv, s + u);
+        if (c + s + u < len) {
+          row_load<BF, NQ>(x, ldx, src, col, xv[u]);
+        } else {
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) xv[u][q] = idle;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          const float4 xw = row4_f32(xv[u][q]);
+          const float* xf = reinterpret_cast<const float*>(&xw);
+#pragma unroll
+          for (int t = 0; t < 4; ++t) acc[4 * q + t] = fold.combine(acc[4 * q + t], xf[t]);
+        }
+      }
+    }
+    idxv = idxn;
+  }
+  if (len > 0) slab_store<(NT & 2) != 0>(slabs + d.k * F + col, acc);
+}
+
 template <int VW, int U, bool WEIGHTED, int NT = 0, bool ATT = false, int SFC = -1, int G = 16, bool SH = false,
           bool BF = false>
 // NT bit 0: non-temporal index/weight loads, bit 1: slab stores; SFC >= 0: the ATT special function
@@ -1056,24 +1223,22 @@ __global__ void __launch_bounds__(kBlock)
 k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
            int64_t ldx, const float* __restrict__ w, int64_t ldw, int lph, float* __restrict__ slabs,
            const SegItem* __restrict__ items, AttArgs att = AttArgs{}) {
+  if constexpr (!WEIGHTED && !ATT) {  // the plain sum: the shared walk
+    seg4_walk<VW, U, G, NT, BF>(indices, n_items_p, x, ldx, slabs, items, FoldSum<BF>{});
+    return;
+  }
   constexpr int F = G * VW;
-  constexpr int IPW = kWave / G;  // items per wave
   constexpr int NQ = VW / 4;
   const int lane = threadIdx.x & (kWave - 1);
   const int l16 = lane & (G - 1);
-  const int64_t k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * IPW + lane / G;
-  const int64_t n_items = *n_items_p;
-  SegItem it{0, 0, 0};
-  if (k < n_items) it = items[k];
-  const int len = it.len;
-  int mx = len;
-#pragma unroll
-  for (int off = G; off < kWave; off <<= 1) mx = max(mx, __shfl_xor(mx, off));
-  const int maxlen = __builtin_amdgcn_readfirstlane(mx);
+  const ItemSlot d = item_decode<G>(n_items_p, items, lane);
+  const int64_t k = d.k;
+  const SegItem it = d.it;
+  const int len = it.len, maxlen = d.maxlen;
   if (maxlen == 0) return;
   const int64_t eb = it.beg;
   const int col = l16 * VW;
-  const int head = (WEIGHTED || ATT) ? l16 / lph : 0;
+  const int head = l16 / lph;
   float acc[VW];
 #pragma unroll
   for (int q = 0; q < VW; ++q) acc[q] = 0.f;
@@ -1095,37 +1260,20 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
         const int src = bcastG<G>(idxv, s + u);
         const bool ok = c + s + u < len;
         if (ok) {
-          if constexpr (BF) {  // the lane's VW bf16: one 8-B load (VW = 4) or 16-B loads (VW = 16)
-            const uint16_t* pb = reinterpret_cast<const uint16_t*>(x) + static_cast<int64_t>(src) * ldx + col;
-            if constexpr (NQ % 2 == 0) {
-#pragma unroll
-              for (int q = 0; q < NQ; q += 2) {
-                const uint4 t = reinterpret_cast<const uint4*>(pb)[q / 2];
-                xv[u][q] = make_uint2(t.x, t.y);
-                xv[u][q + 1] = make_uint2(t.z, t.w);
-              }
-            } else {
-#pragma unroll
-              for (int q = 0; q < NQ; ++q) xv[u][q] = reinterpret_cast<const uint2*>(pb)[q];
-            }
-          } else {
-          const float4* p = reinterpret_cast<const float4*>(x + static_cast<int64_t>(src) * ldx + col);
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) xv[u][q] = p[q];
-          }
+          row_load<BF, NQ>(x, ldx, src, col, xv[u]);
           if (ATT) {
             const float sv = arow + att.b[static_cast<int64_t>(src) * att.ldb + head];
             if (SH) wu[u] = (SFC >= 0) ? sf_shift(SFC, sv, mrow) : sf_shift(att.sf, sv, mrow);
             else wu[u] = (SFC >= 0) ? sf_apply(SFC, sv) : sf_apply(att.sf, sv);
             ssum += wu[u];
-          } else if (WEIGHTED) {
+          } else {
             const float* wp = w + (eb + c + s + u) * ldw + head;
             wu[u] = (NT & 1) ? __builtin_nontemporal_load(wp) : *wp;
           }
         } else {
 #pragma unroll
           for (int q = 0; q < NQ; ++q) xv[u][q] = Row4<BF>::zero();
-          if (WEIGHTED || ATT) wu[u] = 0.f;
+          wu[u] = 0.f;
         }
       }
 #pragma unroll
@@ -1135,8 +1283,7 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
           const float4 xw = row4_f32(xv[u][q]);
           const float* xf = reinterpret_cast<const float*>(&xw);
 #pragma unroll
-          for (int t = 0; t < 4; ++t)
-            acc[4 * q + t] = (WEIGHTED || ATT) ? fmaf(wu[u], xf[t], acc[4 * q + t]) : acc[4 * q + t] + xf[t];
+          for (int t = 0; t < 4; ++t) acc[4 * q + t] = fmaf(wu[u], xf[t], acc[4 * q + t]);
         }
       }
     }
@@ -1144,12 +1291,7 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
   }
   if (len > 0) {
     const int64_t lds = ATT ? F + ((att.H + 3) & ~3) : F;  // sums padded to 16 B
-    float* o = slabs + k * lds + col;
-#pragma unroll
-    for (int q = 0; q < VW; ++q) {
-      if (NT & 2) __builtin_nontemporal_store(acc[q], o + q);
-      else o[q] = acc[q];
-    }
+    slab_store<(NT & 2) != 0>(slabs + k * lds + col, acc);
     if (ATT && l16 % lph == 0) slabs[k * lds + F + head] = ssum;
   }
 }
@@ -1192,22 +1334,76 @@ __device__ __forceinline__ float xmask4(float v, bool odd_quad) {
 // loads were ~19 % of the kernel's vector-memory instructions; the texture path is its bound.)
 // BF: bf16 rows in the same lane layout with half-width loads -- 32 lanes x 8 B, one 256-B row per
 // half-wave instruction (row_bytes = 2 ldx; the host guards are restated for 2-byte elements).
+// The unweighted lean walk (k_agg_h32 without weights, k_red_h32): seg4_walk's chunks and steps at
+// G = 32, U = 8 with lean row addressing and the full / tail split.  NT bit 0: non-temporal index
+// loads, bit 1: non-temporal slab stores.
+template <int NT, bool BF, class Fold>
+__device__ __forceinline__ void h32_walk(const int32_t* indices, const int64_t* n_items_p,
+                                         const float* x, uint32_t row_bytes, float* slabs,
+                                         const SegItem* items, Fold fold) {
+  constexpr int G = 32, F = 128, U = 8;
+  typedef typename Row4<BF>::type XR;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int l32 = lane & (G - 1);
+  const ItemSlot d = item_decode<G>(n_items_p, items, lane);
+  const int len = d.it.len, maxlen = d.maxlen, minlen = d.minlen;
+  if (maxlen == 0) return;
+  const uint32_t colb = static_cast<uint32_t>(l32) * (BF ? 8u : 16u);
+  const char* xb = reinterpret_cast<const char*>(x);
+  const int32_t* ic = indices + d.it.beg;  // chunk cursor: advanced once per 32 edges
+  const XR idle = fold.idle();
+  float acc[4] = {Fold::kInit, Fold::kInit, Fold::kInit, Fold::kInit};
+  auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
+  int idxv = (l32 < len) ? ldi(ic + l32) : 0;
+  for (int c = 0; c < maxlen; c += G) {
+    const int idxn = (c + G + l32 < len) ? ldi(ic + G + l32) : 0;
+#pragma unroll
+    for (int s = 0; s < G; s += U) {
+      if (c + s >= maxlen) break;
+      XR xv[U];
+      if (c + s + U <= minlen) {  // full step for both items: no masks
+#pragma unroll
+        for (int u = 0; u < U; ++u) xv[u] = lean_at<XR>(xb, bcastG<G>(idxv, s + u), row_bytes, colb);
+      } else {
+        const int rem = len - c - s;  // edges of this item left at this step (may be <= 0)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int src = bcastG<G>(idxv, s + u);
+          if (u < rem) xv[u] = lean_at<XR>(xb, src, row_bytes, colb);
+          else xv[u] = idle;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float4 xw = row4_f32(xv[u]);
+        acc[0] = fold.combine(acc[0], xw.x);
+        acc[1] = fold.combine(acc[1], xw.y);
+        acc[2] = fold.combine(acc[2], xw.z);
+        acc[3] = fold.combine(acc[3], xw.w);
+      }
+    }
+    idxv = idxn;
+    ic += G;
+  }
+  if (len > 0) slab_store<(NT & 2) != 0>(slabs + d.k * F + l32 * 4, acc);
+}
+
 template <bool WEIGHTED, int NT, bool W1 = false, bool A1 = false, bool BF = false>
 __global__ void __launch_bounds__(kBlock)
 k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
           uint32_t row_bytes, const float* __restrict__ w, int64_t ldw, float* __restrict__ slabs,
           const SegItem* __restrict__ items) {
+  if constexpr (!WEIGHTED) {  // the plain sum: the shared walk
+    h32_walk<NT, BF>(indices, n_items_p, x, row_bytes, slabs, items, FoldSum<BF>{});
+    return;
+  }
   constexpr int G = 32, F = 128, U = 8;
   const int lane = threadIdx.x & (kWave - 1);
   const int l32 = lane & (G - 1);
-  const int64_t k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * 2 + (lane >> 5);
-  const int64_t n_items = *n_items_p;
-  SegItem it{0, 0, 0};
-  if (k < n_items) it = items[k];
-  const int len = it.len;
-  const int other = __shfl_xor(len, 32);
-  const int maxlen = __builtin_amdgcn_readfirstlane(max(len, other));
-  const int minlen = __builtin_amdgcn_readfirstlane(min(len, other));
+  const ItemSlot d = item_decode<G>(n_items_p, items, lane);
+  const int64_t k = d.k;
+  const SegItem it = d.it;
+  const int len = it.len, maxlen = d.maxlen, minlen = d.minlen;
   if (maxlen == 0) return;
   typedef typename Row4<BF>::type XR;
   const uint32_t colb = static_cast<uint32_t>(l32) * (BF ? 8u : 16u);
@@ -1216,7 +1412,7 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   const int ldw32 = static_cast<int>(ldw);
   // chunk cursors: advanced once per 32 edges, so no per-edge 64-bit offsets are live
   const int32_t* ic = indices + it.beg;
-  const float* wc = (WEIGHTED && !A1) ? w + it.beg * ldw + (W1 ? 0 : h) : nullptr;
+  const float* wc = !A1 ? w + it.beg * ldw + (W1 ? 0 : h) : nullptr;
   // A1: the weights as the uniform base w + a 32-bit byte offset (host: nnz * ldw * 4 < 2^32), like
   // the rows -- with 64-bit per-lane pointers the compiler strength-reduced every (step, edge)
   // weight address into its own 64-bit induction variable (134 VGPRs, 3 waves per SIMD)
@@ -1229,9 +1425,7 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   // once), bit 1: non-temporal slab stores
   auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
   auto ldw_ = [&](const float* p) { return (NT & 4) ? __builtin_nontemporal_load(p) : *p; };
-  auto row = [&](int src) -> XR {
-    return *reinterpret_cast<const XR*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
-  };
+  auto row = [&](int src) { return lean_at<XR>(xb, src, row_bytes, colb); };
   int idxv = (l32 < len) ? ldi(ic + l32) : 0;
   float wv = (W1 && l32 < len) ? ldw_(wc + l32 * ldw32) : 0.f;  // W1: this chunk's weights, lane = edge
   for (int c = 0; c < maxlen; c += G) {
@@ -1245,10 +1439,10 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
       if (c + s + U <= minlen) {  // full step for both items: no masks
 #pragma unroll
         for (int u = 0; u < U; ++u) xv[u] = row(bcastG<G>(idxv, s + u));
-        if (WEIGHTED && W1) {
+        if (W1) {
 #pragma unroll
           for (int u = 0; u < U; ++u) wu[u] = __int_as_float(bcastG<G>(__float_as_int(wv), s + u));
-        } else if (WEIGHTED && A1) {
+        } else if (A1) {
           const float2 pr = *reinterpret_cast<const float2*>(
               wbase + (woff + static_cast<uint32_t>((h & 1) + s + 2 * q) * wrow + static_cast<uint32_t>(2 * (h >> 1) - h) * 4u));
           const bool odd = h & 1;
@@ -1263,7 +1457,7 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
             wu[2 * k2] = odd ? b[k2] : a[k2];
             wu[2 * k2 + 1] = odd ? a[k2] : b[k2];
           }
-        } else if (WEIGHTED) {
+        } else {
           const float* wp = wc + (s + 2 * q) * ldw32;
           const float w0 = ldw_(wp), w1 = ldw_(wp + ldw32);
           wu[0] = quad_bcast<0>(w0); wu[1] = quad_bcast<0>(w1);
@@ -1278,220 +1472,48 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
           const int src = bcastG<G>(idxv, s + u);
           if (u < rem) {
             xv[u] = row(src);
-            if (WEIGHTED)
-              wu[u] = W1 ? __int_as_float(bcastG<G>(__float_as_int(wv), s + u))
-                         : (A1 ? wat(woff + static_cast<uint32_t>(s + u) * wrow) : ldw_(wc + (s + u) * ldw32));
+            wu[u] = W1 ? __int_as_float(bcastG<G>(__float_as_int(wv), s + u))
+                       : (A1 ? wat(woff + static_cast<uint32_t>(s + u) * wrow) : ldw_(wc + (s + u) * ldw32));
           } else {
             xv[u] = Row4<BF>::zero();
-            if (WEIGHTED) wu[u] = 0.f;
+            wu[u] = 0.f;
           }
         }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const float4 xw = row4_f32(xv[u]);
-        if (WEIGHTED) {
-          acc[0] = fmaf(wu[u], xw.x, acc[0]);
-          acc[1] = fmaf(wu[u], xw.y, acc[1]);
-          acc[2] = fmaf(wu[u], xw.z, acc[2]);
-          acc[3] = fmaf(wu[u], xw.w, acc[3]);
-        } else {
-          acc[0] += xw.x; acc[1] += xw.y; acc[2] += xw.z; acc[3] += xw.w;
-        }
+        acc[0] = fmaf(wu[u], xw.x, acc[0]);
+        acc[1] = fmaf(wu[u], xw.y, acc[1]);
+        acc[2] = fmaf(wu[u], xw.z, acc[2]);
+        acc[3] = fmaf(wu[u], xw.w, acc[3]);
       }
     }
     idxv = idxn;
     if (W1) wv = wvn;
     ic += G;
-    if (WEIGHTED && A1) woff += static_cast<uint32_t>(G) * wrow;
-    else if (WEIGHTED) wc += static_cast<int64_t>(G) * ldw;
+    if (A1) woff += static_cast<uint32_t>(G) * wrow;
+    else wc += static_cast<int64_t>(G) * ldw;
   }
-  if (len > 0) {
-    float* o = slabs + k * F + l32 * 4;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      if (NT & 2) __builtin_nontemporal_store(acc[t], o + t);
-      else o[t] = acc[t];
-    }
-  }
+  if (len > 0) slab_store<(NT & 2) != 0>(slabs + k * F + l32 * 4, acc);
 }
 
-// ---------------------------------------------------------------------------
-// Column-blocked MAX / MIN (gta_reduce_blocked): the unweighted item kernels with gta_reduce's
-// reducer in place of the add.  A max cannot ride on the sum's `valid ? t : 0`, so these are
-// kernels of their own: accumulators start at the identity -inf, every value is flipped by the
-// wave-uniform sign bit on its way in (MIN = -max(-x), exact, one instantiation for both) and an
-// idle edge slot holds the identity -- as a bit pattern that the flip turns into -inf
-// (red_idle), so the fold needs no per-edge select and masked lanes issue no loads.  Item k's
-// slab row holds its partial in the MAX domain; k_seg_reduce_red folds and flips back.  An item
-// without edges, or a lane group past n_items, stores nothing.
-// ---------------------------------------------------------------------------
-template <bool BF> struct RedIdle {  // the row piece whose every element flips to -inf
-  static __device__ __forceinline__ float4 make(uint32_t sbit) {
-    const float v = __uint_as_float(0xff800000u ^ sbit);
-    return make_float4(v, v, v, v);
-  }
-};
-template <> struct RedIdle<true> {
-  static __device__ __forceinline__ uint2 make(uint32_t sbit) {
-    const uint32_t h = (0xff800000u ^ sbit) >> 16, v = h | (h << 16);
-    return make_uint2(v, v);
-  }
-};
-
-// k_agg_seg4's unweighted form (same item decode, index broadcast, Row4<BF> loads and lanes):
-// G = 16 for F = 64 / 256 (four items per wave), G = 32 for F = 128 (two; non-temporal slab stores)
+// Column-blocked MAX / MIN (gta_reduce_blocked): the unweighted walks with FoldMax.  Item k's slab
+// row holds its partial in the MAX domain; k_seg_reduce_red folds and flips back.
+// k_red_seg4: G = 16 for F = 64 / 256 (four items per wave), G = 32 for F = 128 (two; non-temporal
+// slab stores).  k_red_h32: the lean F = 128 form.
 template <int VW, int U, int G, bool BF>
 __global__ void __launch_bounds__(kBlock)
 k_red_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
            int64_t ldx, uint32_t sbit, float* __restrict__ slabs, const SegItem* __restrict__ items) {
-  constexpr int F = G * VW;
-  constexpr int IPW = kWave / G;  // items per wave
-  constexpr int NQ = VW / 4;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int l16 = lane & (G - 1);
-  const int64_t k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * IPW + lane / G;
-  const int64_t n_items = *n_items_p;
-  SegItem it{0, 0, 0};
-  if (k < n_items) it = items[k];
-  const int len = it.len;
-  int mx = len;
-#pragma unroll
-  for (int off = G; off < kWave; off <<= 1) mx = max(mx, __shfl_xor(mx, off));
-  const int maxlen = __builtin_amdgcn_readfirstlane(mx);
-  if (maxlen == 0) return;
-  const int64_t eb = it.beg;
-  const int col = l16 * VW;
-  const typename Row4<BF>::type idle = RedIdle<BF>::make(sbit);
-  float acc[VW];
-#pragma unroll
-  for (int q = 0; q < VW; ++q) acc[q] = -__builtin_inff();
-  int idxv = (l16 < len) ? indices[eb + l16] : 0;
-  for (int c = 0; c < maxlen; c += G) {
-    const int idxn = (c + G + l16 < len) ? indices[eb + c + G + l16] : 0;
-#pragma unroll
-    for (int s = 0; s < G; s += U) {
-      if (c + s >= maxlen) break;
-      typename Row4<BF>::type xv[U][NQ];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int src = bcastG<G>(idxv, s + u);
-        if (c + s + u < len) {
-          if constexpr (BF) {  // the lane's VW bf16: one 8-B load (VW = 4) or 16-B loads (VW = 16)
-            const uint16_t* pb = reinterpret_cast<const uint16_t*>(x) + static_cast<int64_t>(src) * ldx + col;
-            if constexpr (NQ % 2 == 0) {
-#pragma unroll
-              for (int q = 0; q < NQ; q += 2) {
-                const uint4 t = reinterpret_cast<const uint4*>(pb)[q / 2];
-                xv[u][q] = make_uint2(t.x, t.y);
-                xv[u][q + 1] = make_uint2(t.z, t.w);
-              }
-            } else {
-#pragma unroll
-              for (int q = 0; q < NQ; ++q) xv[u][q] = reinterpret_cast<const uint2*>(pb)[q];
-            }
-          } else {
-            const float4* p = reinterpret_cast<const float4*>(x + static_cast<int64_t>(src) * ldx + col);
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) xv[u][q] = p[q];
-          }
-        } else {
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) xv[u][q] = idle;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          const float4 xw = row4_f32(xv[u][q]);
-          const float* xf = reinterpret_cast<const float*>(&xw);
-#pragma unroll
-          for (int t = 0; t < 4; ++t) acc[4 * q + t] = red_max(acc[4 * q + t], red_flip(xf[t], sbit));
-        }
-      }
-    }
-    idxv = idxn;
-  }
-  if (len > 0) {
-    float* o = slabs + k * F + col;
-#pragma unroll
-    for (int q = 0; q < VW; ++q) {
-      if (G == 32) __builtin_nontemporal_store(acc[q], o + q);
-      else o[q] = acc[q];
-    }
-  }
+  seg4_walk<VW, U, G, (G == 32 ? 2 : 0), BF>(indices, n_items_p, x, ldx, slabs, items, FoldMax<BF>{sbit});
 }
 
-// Lean F = 128 form, modelled on k_agg_h32<false, ...>: 32-bit row addressing (the host checks
-// n_cols < 2^24 and a table span < 2^32 bytes, in the table's own element size) and unmasked steps
-// where both items still hold 8 edges.  NT bit 0: non-temporal index loads, bit 1: slab stores.
 template <int NT, bool BF>
 __global__ void __launch_bounds__(kBlock)
 k_red_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
           uint32_t row_bytes, uint32_t sbit, float* __restrict__ slabs, const SegItem* __restrict__ items) {
-  constexpr int G = 32, F = 128, U = 8;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int l32 = lane & (G - 1);
-  const int64_t k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * 2 + (lane >> 5);
-  const int64_t n_items = *n_items_p;
-  SegItem it{0, 0, 0};
-  if (k < n_items) it = items[k];
-  const int len = it.len;
-  const int other = __shfl_xor(len, 32);
-  const int maxlen = __builtin_amdgcn_readfirstlane(max(len, other));
-  const int minlen = __builtin_amdgcn_readfirstlane(min(len, other));
-  if (maxlen == 0) return;
-  typedef typename Row4<BF>::type XR;
-  const uint32_t colb = static_cast<uint32_t>(l32) * (BF ? 8u : 16u);
-  const char* xb = reinterpret_cast<const char*>(x);
-  const int32_t* ic = indices + it.beg;  // chunk cursor: advanced once per 32 edges
-  const XR idle = RedIdle<BF>::make(sbit);
-  const float ident = -__builtin_inff();
-  float acc[4] = {ident, ident, ident, ident};
-  auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
-  auto row = [&](int src) -> XR {
-    return *reinterpret_cast<const XR*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
-  };
-  int idxv = (l32 < len) ? ldi(ic + l32) : 0;
-  for (int c = 0; c < maxlen; c += G) {
-    const int idxn = (c + G + l32 < len) ? ldi(ic + G + l32) : 0;
-#pragma unroll
-    for (int s = 0; s < G; s += U) {
-      if (c + s >= maxlen) break;
-      XR xv[U];
-      if (c + s + U <= minlen) {  // full step for both items: no masks
-#pragma unroll
-        for (int u = 0; u < U; ++u) xv[u] = row(bcastG<G>(idxv, s + u));
-      } else {
-        const int rem = len - c - s;  // edges of this item left at this step (may be <= 0)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int src = bcastG<G>(idxv, s + u);
-          if (u < rem) xv[u] = row(src);
-          else xv[u] = idle;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const float4 xw = row4_f32(xv[u]);
-        acc[0] = red_max(acc[0], red_flip(xw.x, sbit));
-        acc[1] = red_max(acc[1], red_flip(xw.y, sbit));
-        acc[2] = red_max(acc[2], red_flip(xw.z, sbit));
-        acc[3] = red_max(acc[3], red_flip(xw.w, sbit));
-      }
-    }
-    idxv = idxn;
-    ic += G;
-  }
-  if (len > 0) {
-    float* o = slabs + k * F + l32 * 4;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      if (NT & 2) __builtin_nontemporal_store(acc[t], o + t);
-      else o[t] = acc[t];
-    }
-  }
+  h32_walk<NT, BF>(indices, n_items_p, x, row_bytes, slabs, items, FoldMax<BF>{sbit});
 }
 
 // Round 6: the metric kernel with its two streamed inputs -- alpha (32 B per edge) and the source
@@ -1540,14 +1562,10 @@ k_agg_h32pf(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_i
   constexpr int NPA = 256 / PFB;  // granules of one item's alpha per step (8 edges x 32 B)
   const int lane = threadIdx.x & (kWave - 1);
   const int l32 = lane & (G - 1);
-  const int64_t k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * 2 + (lane >> 5);
-  const int64_t n_items = *n_items_p;
-  SegItem it{0, 0, 0};
-  if (k < n_items) it = items[k];
-  const int len = it.len;
-  const int other = __shfl_xor(len, 32);
-  const int maxlen = __builtin_amdgcn_readfirstlane(max(len, other));
-  const int minlen = __builtin_amdgcn_readfirstlane(min(len, other));
+  const ItemSlot d = item_decode<G>(n_items_p, items, lane);
+  const int64_t k = d.k;
+  const SegItem it = d.it;
+  const int len = it.len, maxlen = d.maxlen, minlen = d.minlen;
   if (maxlen == 0) return;
   // the two items as scalars (A: lanes 0-31, B: lanes 32-63); edge ids < 2^27 (host: nnz * 32 < 2^32)
   const uint32_t begA = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(it.beg), 0));
@@ -1564,9 +1582,7 @@ k_agg_h32pf(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_i
   auto wat = [&](uint32_t off) { return *reinterpret_cast<const float*>(wbase + off); };
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
-  auto row = [&](int src) -> float4 {
-    return *reinterpret_cast<const float4*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
-  };
+  auto row = [&](int src) { return lean_at<float4>(xb, src, row_bytes, colb); };
   // prefetch bookkeeping: the granules issued at the previous step, kept live until the next wait
   int pfa[2 * NPA], pfi[4];
 #pragma unroll
@@ -1699,14 +1715,7 @@ k_agg_h32pf(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_i
     woff += static_cast<uint32_t>(G) * wrow;
   }
   retire();  // no scalar load in flight when the wave ends
-  if (len > 0) {
-    float* o = slabs + k * F + l32 * 4;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      if (NT & 2) __builtin_nontemporal_store(acc[t], o + t);
-      else o[t] = acc[t];
-    }
-  }
+  if (len > 0) slab_store<(NT & 2) != 0>(slabs + k * F + l32 * 4, acc);
 }
 
 // Lean half-wave form of the fused GAT attention item (k_agg_seg4<4, 8, ATT, SFC = exp-leaky-
@@ -1735,14 +1744,10 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   constexpr int G = 32, U = 8, F = 128, LDS = F + 8;
   const int lane = threadIdx.x & (kWave - 1);
   const int l32 = lane & (G - 1);
-  const int64_t k = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * 2 + (lane >> 5);
-  const int64_t n_items = *n_items_p;
-  SegItem it{0, 0, 0};
-  if (k < n_items) it = items[k];
-  const int len = it.len;
-  const int other = __shfl_xor(len, 32);
-  const int maxlen = __builtin_amdgcn_readfirstlane(max(len, other));
-  const int minlen = __builtin_amdgcn_readfirstlane(min(len, other));
+  const ItemSlot d = item_decode<G>(n_items_p, items, lane);
+  const int64_t k = d.k;
+  const SegItem it = d.it;
+  const int len = it.len, maxlen = d.maxlen, minlen = d.minlen;
   if (maxlen == 0) return;
   const int h = l32 >> 2, q = l32 & 3;
   typedef typename Row4<BF>::type XR;
@@ -1752,11 +1757,9 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   const float arow = (len > 0) ? a[static_cast<int64_t>(it.row) * lda + h] : 0.f;
   const float mrow = (SH && len > 0) ? shift[static_cast<int64_t>(it.row) * 8 + h] : 0.f;
   auto ldi = [&](const int32_t* p) { return (NT & 1) ? __builtin_nontemporal_load(p) : *p; };
-  auto row = [&](int src) -> XR {
-    return *reinterpret_cast<const XR*>(xb + (__umul24(static_cast<uint32_t>(src), row_bytes) + colb));
-  };
+  auto row = [&](int src) { return lean_at<XR>(xb, src, row_bytes, colb); };
   auto score = [&](int src) -> float {
-    const float sv = arow + *reinterpret_cast<const float*>(bb + (__umul24(static_cast<uint32_t>(src), brow_bytes) + hb));
+    const float sv = arow + lean_at<float>(bb, src, brow_bytes, hb);
     return SH ? sf_shift(GTA_SF_EXP_LEAKY_RELU, sv, mrow) : sf_apply(GTA_SF_EXP_LEAKY_RELU, sv);
   };
   const int32_t* ic = indices + it.beg;
@@ -1829,11 +1832,7 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
       return;
     }
     float* o = slabs + k * LDS;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      if (NT & 2) __builtin_nontemporal_store(acc[t], o + l32 * 4 + t);
-      else o[l32 * 4 + t] = acc[t];
-    }
+    slab_store<(NT & 2) != 0>(o + l32 * 4, acc);
     if (q == 0) o[F + h] = ssum;
   }
 }
@@ -1865,18 +1864,15 @@ __device__ __forceinline__ void for_row_items(RowItems ri, int64_t row, int lane
   }
 }
 
-template <int VW>
-__global__ void __launch_bounds__(kBlock)
-k_seg_reduce(int64_t n_rows, const float* __restrict__ slabs, const float* __restrict__ row_scale,
-             float* __restrict__ y, int64_t ldy, int accumulate, RowItems ri) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
-  if (row >= n_rows) return;
+// The ordered reduce's body: the lane's VW columns of the row's slab rows folded in item order.
+// k_seg_reduce (FoldSum) and k_seg_reduce_red (FoldMax) differ in the fold and in what they write.
+template <int VW, class Fold>
+__device__ __forceinline__ void seg_reduce_fold(const float* slabs, RowItems ri, int64_t row, int lane,
+                                                Fold fold, float (&acc)[VW]) {
   const int col = lane * VW;
   constexpr int F = kWave * VW;
-  float acc[VW];
 #pragma unroll
-  for (int q = 0; q < VW; ++q) acc[q] = 0.f;
+  for (int q = 0; q < VW; ++q) acc[q] = Fold::kInit;
   for_row_items<VW>(ri, row, lane, [&](int64_t i0, int64_t i1, int64_t i2, int64_t i3, int m) {
     Vec<VW> p[4];
     p[0].load(slabs + i0 * F + col);
@@ -1887,8 +1883,20 @@ k_seg_reduce(int64_t n_rows, const float* __restrict__ slabs, const float* __res
     }
     for (int u = 0; u < m; ++u)
 #pragma unroll
-      for (int q = 0; q < VW; ++q) acc[q] += p[u].v[q];
+      for (int q = 0; q < VW; ++q) acc[q] = fold.combine(acc[q], p[u].v[q]);
   });
+}
+
+template <int VW>
+__global__ void __launch_bounds__(kBlock)
+k_seg_reduce(int64_t n_rows, const float* __restrict__ slabs, const float* __restrict__ row_scale,
+             float* __restrict__ y, int64_t ldy, int accumulate, RowItems ri) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  if (row >= n_rows) return;
+  const int col = lane * VW;
+  float acc[VW];
+  seg_reduce_fold<VW>(slabs, ri, row, lane, FoldSum<false>{}, acc);
   const float scale = row_scale ? row_scale[row] : 1.f;
   float* yp = y + row * ldy + col;
   Vec<VW> o;
@@ -1914,23 +1922,9 @@ k_seg_reduce_red(int64_t n_rows, const float* __restrict__ slabs, uint32_t sbit,
   const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
   if (row >= n_rows) return;
   const int col = lane * VW;
-  constexpr int F = kWave * VW;
   const bool empty = ri.row_ptr[row] == ri.row_ptr[row + 1];
   float acc[VW];
-#pragma unroll
-  for (int q = 0; q < VW; ++q) acc[q] = -__builtin_inff();
-  for_row_items<VW>(ri, row, lane, [&](int64_t i0, int64_t i1, int64_t i2, int64_t i3, int m) {
-    Vec<VW> p[4];
-    p[0].load(slabs + i0 * F + col);
-    if (m == 4) {
-      p[1].load(slabs + i1 * F + col);
-      p[2].load(slabs + i2 * F + col);
-      p[3].load(slabs + i3 * F + col);
-    }
-    for (int u = 0; u < m; ++u)
-#pragma unroll
-      for (int q = 0; q < VW; ++q) acc[q] = red_max(acc[q], p[u].v[q]);
-  });
+  seg_reduce_fold<VW>(slabs, ri, row, lane, FoldMax<false>{0u}, acc);  // partials are in the MAX domain: no flip
   Vec<VW> o;
 #pragma unroll
   for (int q = 0; q < VW; ++q) o.v[q] = empty ? 0.f : red_flip(acc[q], sbit);
@@ -4917,6 +4911,64 @@ int reduce_impl(int red, const int64_t* indptr, const int32_t* indices, int64_t 
   if (combined) GTA_LAUNCHED("k_reduce_combine");
   return GTA_OK;
 }
+
+// ---- host side of the column-blocked entry points (aggregate, reduce, GAT aggregate) ----
+
+// What the three families read from a blocked plan and its workspace: built after the family's own
+// argument checks, it touches no memory (pointer arithmetic on the plan's layout and the grids).
+struct BlockedCall {
+  BlockedView v;
+  RowItems ri;
+  float* slabs;        // per-item slab rows (the workspace)
+  const int64_t* nit;  // the plan's n_items, read by the kernels
+  const SegItem* its;
+  int64_t items;       // grid bound (blocked_max_items); the kernels stop at *nit
+  dim3 g2, g2h, g4;    // item grids: one, two (half-wave) and four (quarter-wave) items per wave
+  dim3 g3;             // the ordered reduce: one wave per row
+  dim3 blk{kBlock};
+  hipStream_t s;
+  BlockedCall(const void* plan, int64_t n_rows, int64_t nnz, int64_t blocks, int64_t item_edges, void* workspace,
+              void* stream)
+      : items(blocked_max_items(n_rows, nnz, static_cast<int>(blocks), item_edges)), s(S(stream)) {
+    v = blocked_view(const_cast<void*>(plan), n_rows, static_cast<int>(blocks), items);
+    ri = RowItems{v.row_ptr, v.row_items};
+    slabs = static_cast<float*>(workspace);
+    nit = &v.hdr[4];
+    its = v.items;
+    auto grid = [](int64_t n, int per_block) { return dim3(static_cast<unsigned>((n + per_block - 1) / per_block)); };
+    g2 = grid(items, kWavesPerBlock);
+    g2h = grid(items, 2 * kWavesPerBlock);
+    g4 = grid(items, 4 * kWavesPerBlock);
+    g3 = grid(n_rows, kWavesPerBlock);
+  }
+};
+
+// The lean kernels' 32-bit row addressing (lean_at): row ids fit the 24-bit multiply and the table
+// spans < 2^32 bytes, in the table's own element size
+inline bool lean32_ok(int64_t n_cols, int64_t ld, unsigned elem_bytes) {
+  return n_cols < (1 << 24) && static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ld) * elem_bytes < (1ull << 32);
+}
+
+// Run-time bools as compile-time constants for a generic lambda, next to dispatch_lpe's IC:
+// with_bools(fn, a, b) calls fn(BC<a>{}, BC<b>{}), so a ladder over template flags is written once.
+template <bool V>
+using BC = std::integral_constant<bool, V>;
+
+template <class Fn>
+void with_bools(Fn fn) { fn(); }
+template <class Fn, class... Rest>
+void with_bools(Fn fn, bool b, Rest... rest) {
+  if (b) with_bools([&](auto... cs) { fn(BC<true>{}, cs...); }, rest...);
+  else with_bools([&](auto... cs) { fn(BC<false>{}, cs...); }, rest...);
+}
+
+// The ordered reduce's ladder (k_seg_reduce, k_seg_reduce_red, k_seg_reduce_att): fn(VW), VW = F / 64
+template <class Fn>
+void launch_seg_reduce(int vw, Fn fn) {
+  if (vw == 2) fn(IC<2>{});
+  else if (vw == 4) fn(IC<4>{});
+  else fn(IC<1>{});
+}
 }  // namespace
 extern "C" {
 
@@ -5082,18 +5134,9 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
     gl_ok = (F / heads) % vw == 0 && (gl == 4 || gl == 8 || gl == 16);
   }
   const std::string gl_msg = who + ": (F/heads)/VW must be 4, 8 or 16 (or quarter-wave lanes per head 1..16)";
-  const int B = static_cast<int>(blocks);
-  const int64_t mi = blocked_max_items(n_rows, nnz, B, item_edges);
-  BlockedView v = blocked_view(const_cast<void*>(plan), n_rows, B, mi);
-  hipStream_t s = S(stream);
+  const BlockedCall c(plan, n_rows, nnz, blocks, item_edges, workspace, stream);
   if (!workspace && nnz > 0) return fail(GTA_ERR_ARG, who + ": needs the slab workspace");
   // one launch over the plan's items into per-item slab rows, then the ordered reduce
-  const RowItems ri{v.row_ptr, v.row_items};
-  float* slabs = static_cast<float*>(workspace);
-  const int64_t items = mi;  // grid bound; the kernels stop at the plan's n_items
-  const int64_t* nit = &v.hdr[4];
-  const SegItem* its = v.items;
-  const dim3 g2(static_cast<unsigned>((items + kWavesPerBlock - 1) / kWavesPerBlock)), blk2(kBlock);
   const int vq = static_cast<int>(F / 16);
   const int lph = w ? static_cast<int>((F / heads) / vq) : 0;
   // multi-item waves (F = 64 / 256: four 16-lane items; F = 128: two 32-lane items, one 512-B row per
@@ -5105,13 +5148,18 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
                                            "multi-item forms (F/heads a multiple of F/16, lanes per head dividing 16)");
   const int phase = tuning().seg_phase;
   const unsigned xe = bf ? 2u : 4u;  // bytes per gathered element
-  if (items == 0 || phase == 2) {
+  // the generic G-lane form <VW, U, WEIGHTED, NT, no ATT, G, BF>, fp32 and bf16, weighted or not
+  auto seg4 = [&](auto VW, auto U, auto NT, auto G, dim3 grid, int lanes_per_head) {
+    with_bools([&](auto W, auto BF) {
+      k_agg_seg4<VW(), U(), W(), NT(), false, -1, G(), false, BF()><<<grid, c.blk, 0, c.s>>>(
+          indices, c.nit, x, ldx, w, ldw, lanes_per_head, c.slabs, c.its);
+    }, w != nullptr, bf);
+  };
+  if (c.items == 0 || phase == 2) {
     // no edges: no items; the reduce below writes the (empty) rows (phase 2: the reduce only)
   } else if (quarter && vq == 8) {  // F = 128: half-wave items, 32 lanes x float4 (bf16: x 8 B)
     const int lph32 = w ? static_cast<int>((F / heads) / 4) : 0;
-    const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
-    const bool lean = tuning().seg_lean && n_cols < (1 << 24) &&
-                      static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * xe < (1ull << 32) &&
+    const bool lean = tuning().seg_lean && lean32_ok(n_cols, ldx, xe) &&
                       (!w || lph32 == 4 || (heads == 1 && tuning().seg_lean_w1 && ldw < (int64_t(1) << 24)));
     const uint32_t rb = static_cast<uint32_t>(ldx * xe);
     // NT template bits: 1 = non-temporal index loads, 2 = non-temporal slab stores (measured -0.5 % / -1 %;
@@ -5121,44 +5169,36 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
                       static_cast<uint64_t>(nnz) * static_cast<uint64_t>(ldw) * 4u < (1ull << 32);
       const int pf = tuning().seg_pf;
       const uint32_t wbytes = static_cast<uint32_t>(nnz * ldw * 4), ibytes = static_cast<uint32_t>(nnz * 4);
-      if (bf) {
-        if (w && heads == 1) k_agg_h32<true, 2, true, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
-        else if (a1) k_agg_h32<true, 3, false, true, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
-        else if (w) k_agg_h32<true, 3, false, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
-        else k_agg_h32<false, 2, false, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
-      } else if (w && heads == 1) k_agg_h32<true, 2, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
-      else if (a1 && ldw == 8 && pf >= 1 && pf <= 5) {
-#define GTA_PF(PFB_, PD_) k_agg_h32pf<3, PFB_, PD_><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its, wbytes, ibytes)
+      auto h32 = [&](auto W, auto NT, auto W1, auto A1) {  // k_agg_h32<WEIGHTED, NT, W1, A1, BF>
+        with_bools([&](auto BF) {
+          k_agg_h32<W(), NT(), W1(), A1(), BF()><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, w, ldw, c.slabs, c.its);
+        }, bf);
+      };
+      constexpr BC<true> yes{};
+      constexpr BC<false> no{};
+      if (w && heads == 1) h32(yes, IC<2>{}, yes, no);
+      else if (!bf && a1 && ldw == 8 && pf >= 1 && pf <= 5) {  // the scalar-prefetch form has no bf16 twin
+#define GTA_PF(PFB_, PD_) \
+  k_agg_h32pf<3, PFB_, PD_><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, w, ldw, c.slabs, c.its, wbytes, ibytes)
         if (pf == 1) GTA_PF(64, 0); else if (pf == 2) GTA_PF(128, 0); else if (pf == 3) GTA_PF(64, 1); else if (pf == 4) GTA_PF(128, 1);
-        else k_agg_h32pf<3, 64, 0, 8><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its, wbytes, ibytes);
+        else k_agg_h32pf<3, 64, 0, 8><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, w, ldw, c.slabs, c.its, wbytes, ibytes);
 #undef GTA_PF
-      } else if (a1) k_agg_h32<true, 3, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
-      else if (w) k_agg_h32<true, 3><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
-      else k_agg_h32<false, 2><<<g2h, blk2, 0, s>>>(indices, nit, x, rb, w, ldw, slabs, its);
+      } else if (a1) h32(yes, IC<3>{}, no, yes);
+      else if (w) h32(yes, IC<3>{}, no, no);
+      else h32(no, IC<2>{}, no, no);
       GTA_LAUNCHED("k_agg_h32");
     } else {
-      if (bf && w) k_agg_seg4<4, 8, true, 2, false, -1, 32, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph32, slabs, its);
-      else if (bf) k_agg_seg4<4, 8, false, 2, false, -1, 32, false, true><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, 0, slabs, its);
-      else if (w) k_agg_seg4<4, 8, true, 2, false, -1, 32><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph32, slabs, its);
-      else k_agg_seg4<4, 8, false, 2, false, -1, 32><<<g2h, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, 0, slabs, its);
+      seg4(IC<4>{}, IC<8>{}, IC<2>{}, IC<32>{}, c.g2h, lph32);
       GTA_LAUNCHED("k_agg_seg4<half>");
     }
   } else if (quarter) {  // F = 64 / 256: quarter-wave items
-    const dim3 g4(static_cast<unsigned>((items + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock)));
-#define GTA_SEG4(VW_, U_)                                                                               \
-  if (bf && w) k_agg_seg4<VW_, U_, true, 0, false, -1, 16, false, true><<<g4, blk2, 0, s>>>(           \
-      indices, nit, x, ldx, w, ldw, lph, slabs, its);                                                  \
-  else if (bf) k_agg_seg4<VW_, U_, false, 0, false, -1, 16, false, true><<<g4, blk2, 0, s>>>(          \
-      indices, nit, x, ldx, w, ldw, lph, slabs, its);                                                  \
-  else if (w) k_agg_seg4<VW_, U_, true><<<g4, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph, slabs, its); \
-  else k_agg_seg4<VW_, U_, false><<<g4, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, lph, slabs, its)
-    if (vq == 4) { GTA_SEG4(4, 4); } else { GTA_SEG4(16, 2); }
-#undef GTA_SEG4
+    if (vq == 4) seg4(IC<4>{}, IC<4>{}, IC<0>{}, IC<16>{}, c.g4, lph);
+    else seg4(IC<16>{}, IC<2>{}, IC<0>{}, IC<16>{}, c.g4, lph);
     GTA_LAUNCHED("k_agg_seg4");
   } else {
     if (!gl_ok) return fail(GTA_ERR_UNSUPPORTED, gl_msg);
 #define GTA_SEG2D(VW_, GL_) \
-  k_agg_seg2d<VW_, GL_><<<g2, blk2, 0, s>>>(indices, nit, x, ldx, w, ldw, slabs, its)
+  k_agg_seg2d<VW_, GL_><<<c.g2, c.blk, 0, c.s>>>(indices, c.nit, x, ldx, w, ldw, c.slabs, c.its)
     if (vw == 2) {
       if (gl == 0) GTA_SEG2D(2, 0); else if (gl == 4) GTA_SEG2D(2, 4); else if (gl == 8) GTA_SEG2D(2, 8); else GTA_SEG2D(2, 16);
     } else if (vw == 4) {
@@ -5170,10 +5210,9 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
     GTA_LAUNCHED("k_agg_seg2d");
   }
   if (phase == 1) return GTA_OK;  // the item launch only; a later phase-2 call reduces
-  const dim3 g3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
-  if (vw == 2) k_seg_reduce<2><<<g3, blk2, 0, s>>>(n_rows, slabs, row_scale, y, ldy, accumulate, ri);
-  else if (vw == 4) k_seg_reduce<4><<<g3, blk2, 0, s>>>(n_rows, slabs, row_scale, y, ldy, accumulate, ri);
-  else k_seg_reduce<1><<<g3, blk2, 0, s>>>(n_rows, slabs, row_scale, y, ldy, accumulate, ri);
+  launch_seg_reduce(vw, [&](auto V) {
+    k_seg_reduce<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, row_scale, y, ldy, accumulate, c.ri);
+  });
   GTA_LAUNCHED("k_seg_reduce");
   return GTA_OK;
 }
@@ -5224,49 +5263,36 @@ int gta_reduce_blocked(int red, const int64_t* indptr, const int32_t* indices, i
   if (!vw) return fail(GTA_ERR_UNSUPPORTED, who + ": F must be 64, 128 or 256 with y rows aligned to F/64 floats");
   if (nnz > 0 && (ldx % (bf ? 8 : 4) != 0 || !aligned(xv, 16)))  // multi-item forms only: no one-item-per-wave twin
     return fail(GTA_ERR_UNSUPPORTED, who + ": x must be 16-B aligned with ldx % 4 == 0 (fp32) or ldx % 8 == 0 (bf16)");
-  const int B = static_cast<int>(blocks);
-  const int64_t items = blocked_max_items(n_rows, nnz, B, item_edges);  // grid bound; the kernels stop at n_items
-  BlockedView v = blocked_view(const_cast<void*>(plan), n_rows, B, items);
-  hipStream_t s = S(stream);
-  const RowItems ri{v.row_ptr, v.row_items};
-  float* slabs = static_cast<float*>(workspace);
+  const BlockedCall c(plan, n_rows, nnz, blocks, item_edges, workspace, stream);
   const float* x = static_cast<const float*>(xv);  // bf: bf16 rows, read as such by the BF kernels only
-  const int64_t* nit = &v.hdr[4];
-  const SegItem* its = v.items;
   const uint32_t sbit = red == GTA_RED_MIN ? 0x80000000u : 0u;
   const unsigned xe = bf ? 2u : 4u;  // bytes per gathered element
-  const dim3 blk(kBlock);
-  if (items == 0) {
+  auto seg4 = [&](auto VW, auto U, auto G, dim3 grid) {  // k_red_seg4<VW, U, G, BF>
+    with_bools([&](auto BF) {
+      k_red_seg4<VW(), U(), G(), BF()><<<grid, c.blk, 0, c.s>>>(indices, c.nit, x, ldx, sbit, c.slabs, c.its);
+    }, bf);
+  };
+  if (c.items == 0) {
     // no edges: no items; the reduce below writes the (empty) rows
   } else if (F == 128) {  // half-wave items
-    const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
-    const bool lean = tuning().seg_lean && n_cols < (1 << 24) &&
-                      static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * xe < (1ull << 32);
-    if (lean) {
+    if (tuning().seg_lean && lean32_ok(n_cols, ldx, xe)) {
       const uint32_t rb = static_cast<uint32_t>(ldx * xe);
-      if (bf) k_red_h32<2, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, sbit, slabs, its);
-      else k_red_h32<2, false><<<g2h, blk, 0, s>>>(indices, nit, x, rb, sbit, slabs, its);
+      with_bools([&](auto BF) {
+        k_red_h32<2, BF()><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, sbit, c.slabs, c.its);
+      }, bf);
       GTA_LAUNCHED("k_red_h32");
     } else {
-      if (bf) k_red_seg4<4, 8, 32, true><<<g2h, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
-      else k_red_seg4<4, 8, 32, false><<<g2h, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
+      seg4(IC<4>{}, IC<8>{}, IC<32>{}, c.g2h);
       GTA_LAUNCHED("k_red_seg4<half>");
     }
   } else {  // F = 64 / 256: quarter-wave items
-    const dim3 g4(static_cast<unsigned>((items + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock)));
-    if (F == 64) {
-      if (bf) k_red_seg4<4, 4, 16, true><<<g4, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
-      else k_red_seg4<4, 4, 16, false><<<g4, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
-    } else {
-      if (bf) k_red_seg4<16, 2, 16, true><<<g4, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
-      else k_red_seg4<16, 2, 16, false><<<g4, blk, 0, s>>>(indices, nit, x, ldx, sbit, slabs, its);
-    }
+    if (F == 64) seg4(IC<4>{}, IC<4>{}, IC<16>{}, c.g4);
+    else seg4(IC<16>{}, IC<2>{}, IC<16>{}, c.g4);
     GTA_LAUNCHED("k_red_seg4");
   }
-  const dim3 g3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
-  if (vw == 2) k_seg_reduce_red<2><<<g3, blk, 0, s>>>(n_rows, slabs, sbit, y, ldy, ri);
-  else if (vw == 4) k_seg_reduce_red<4><<<g3, blk, 0, s>>>(n_rows, slabs, sbit, y, ldy, ri);
-  else k_seg_reduce_red<1><<<g3, blk, 0, s>>>(n_rows, slabs, sbit, y, ldy, ri);
+  launch_seg_reduce(vw, [&](auto V) {
+    k_seg_reduce_red<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, sbit, y, ldy, c.ri);
+  });
   GTA_LAUNCHED("k_seg_reduce_red");
   return GTA_OK;
 }
@@ -5309,87 +5335,47 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
                                                           "a multiple of F/16");
   const int lph = static_cast<int>((F / heads) / vq);
   if (lph < 1 || 16 % lph) return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": lanes per head must divide 16");
-  const int B = static_cast<int>(blocks);
-  const int64_t mi = blocked_max_items(n_rows, nnz, B, item_edges);
-  BlockedView v = blocked_view(const_cast<void*>(plan), n_rows, B, mi);
-  const RowItems ri{v.row_ptr, v.row_items};
-  hipStream_t s = S(stream);
-  float* slabs = static_cast<float*>(workspace);
+  const BlockedCall c(plan, n_rows, nnz, blocks, item_edges, workspace, stream);
   AttArgs att{a_dst, lda, b_src, ldb, sf, static_cast<int>(heads), shift};
-  const int64_t items = mi;
-  const int64_t* nit = &v.hdr[4];
-  const dim3 g4(static_cast<unsigned>((items + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock))), blk(kBlock);
-  const SegItem* it = v.items;
   int skip_single = 0;  // rows whose only item wrote y directly (k_att_h32)
-  if (items > 0) {  // no edges: no items, the reduce alone writes the empty rows
-  const bool elr = sf == GTA_SF_EXP_LEAKY_RELU;  // GAT's score function, specialised
-#define GTA_ATT(VW_, U_)                                                                                          \
-  if (shifted && elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 16, true><<<g4, blk, 0, s>>>(   \
-      indices, nit, x, ldx, nullptr, 0, lph, slabs, it, att);                                            \
-  else if (shifted) k_agg_seg4<VW_, U_, false, 0, true, -1, 16, true><<<g4, blk, 0, s>>>(                        \
-      indices, nit, x, ldx, nullptr, 0, lph, slabs, it, att);                                            \
-  else if (elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU><<<g4, blk, 0, s>>>(                   \
-      indices, nit, x, ldx, nullptr, 0, lph, slabs, it, att);                                            \
-  else k_agg_seg4<VW_, U_, false, 0, true><<<g4, blk, 0, s>>>(indices, nit, x, ldx, nullptr, 0, lph, slabs, \
-                                                             it, att)
-// the bf16 twins: G_ lanes per item on grid GR_, lanes per head LPH_
-#define GTA_ATT_BF(VW_, U_, G_, GR_, LPH_)                                                                        \
-  if (shifted && elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU, G_, true, true><<<GR_, blk, 0, s>>>( \
-      indices, nit, x, ldx, nullptr, 0, LPH_, slabs, it, att);                                           \
-  else if (shifted) k_agg_seg4<VW_, U_, false, 0, true, -1, G_, true, true><<<GR_, blk, 0, s>>>(                 \
-      indices, nit, x, ldx, nullptr, 0, LPH_, slabs, it, att);                                           \
-  else if (elr) k_agg_seg4<VW_, U_, false, 0, true, GTA_SF_EXP_LEAKY_RELU, G_, false, true><<<GR_, blk, 0, s>>>( \
-      indices, nit, x, ldx, nullptr, 0, LPH_, slabs, it, att);                                           \
-  else k_agg_seg4<VW_, U_, false, 0, true, -1, G_, false, true><<<GR_, blk, 0, s>>>(                             \
-      indices, nit, x, ldx, nullptr, 0, LPH_, slabs, it, att)
-  const int lph32 = static_cast<int>((F / heads) / 4);
-  const bool lean = tuning().att_lean && elr && F == 128 && heads == 8 && n_cols < (1 << 24) &&
-                    static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldx) * (bf ? 2u : 4u) < (1ull << 32) &&
-                    static_cast<uint64_t>(n_cols) * static_cast<uint64_t>(ldb) * 4u < (1ull << 32);
-  if (lean) {
-    const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
-    const uint32_t rb = static_cast<uint32_t>(ldx * (bf ? 2 : 4)), bbytes = static_cast<uint32_t>(ldb * 4);
-    // single-item rows are common only when few blocks cut the rows (low degree, B <= 2); above
-    // that the row_ptr reads at every item's end cost more than the rare direct writes save
-    const bool direct = (tuning().att_direct == 2 || (tuning().att_direct == 1 && B <= 2)) && ldy % 4 == 0 && aligned(y, 16);
-    skip_single = direct;
-    const int64_t* rp = direct ? v.row_ptr : nullptr;
-    if (bf && shifted)
-      k_att_h32<2, true, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp,
-                                                   normalize, y, ldy, sums, sf_out, shift);
-    else if (bf)
-      k_att_h32<2, false, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp,
-                                                    normalize, y, ldy, sums, sf_out);
-    else if (shifted)
-      k_att_h32<2, true><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp, normalize,
-                                             y, ldy, sums, sf_out, shift);
-    else
-      k_att_h32<2><<<g2h, blk, 0, s>>>(indices, nit, x, rb, a_dst, lda, b_src, bbytes, slabs, it, rp, normalize, y,
-                                       ldy, sums, sf_out);  // NT bit 2: non-temporal slab stores
-  } else if (F == 128 && (F / heads) % 4 == 0 && lph32 >= 1 && 32 % lph32 == 0) {
-    const dim3 g2h(static_cast<unsigned>((items + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock)));
-    if (bf) { GTA_ATT_BF(4, 8, 32, g2h, lph32); }
-    else if (shifted && elr) k_agg_seg4<4, 8, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 32, true><<<g2h, blk, 0, s>>>(
-        indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
-    else if (shifted) k_agg_seg4<4, 8, false, 0, true, -1, 32, true><<<g2h, blk, 0, s>>>(
-        indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
-    else if (elr) k_agg_seg4<4, 8, false, 0, true, GTA_SF_EXP_LEAKY_RELU, 32><<<g2h, blk, 0, s>>>(
-        indices, nit, x, ldx, nullptr, 0, lph32, slabs, it, att);
-    else k_agg_seg4<4, 8, false, 0, true, -1, 32><<<g2h, blk, 0, s>>>(indices, nit, x, ldx, nullptr, 0,
-                                                                      lph32, slabs, it, att);
-  } else if (bf) {
-    if (vq == 4) { GTA_ATT_BF(4, 4, 16, g4, lph); } else { GTA_ATT_BF(16, 2, 16, g4, lph); }
-  } else if (vq == 4) { GTA_ATT(4, 4); } else { GTA_ATT(16, 2); }
-#undef GTA_ATT_BF
-#undef GTA_ATT
-  GTA_LAUNCHED("k_agg_seg4<att>");
+  if (c.items > 0) {  // no edges: no items, the reduce alone writes the empty rows
+    const bool elr = sf == GTA_SF_EXP_LEAKY_RELU;  // GAT's score function, specialised
+    const unsigned xe = bf ? 2u : 4u;              // bytes per gathered element
+    // the generic G-lane attention form <VW, U, ATT, SFC (elr fixed at compile time), G, SH, BF>
+    auto seg4 = [&](auto VW, auto U, auto G, dim3 grid, int lanes_per_head) {
+      with_bools([&](auto ELR, auto SH, auto BF) {
+        k_agg_seg4<VW(), U(), false, 0, true, (ELR() ? GTA_SF_EXP_LEAKY_RELU : -1), G(), SH(), BF()>
+            <<<grid, c.blk, 0, c.s>>>(indices, c.nit, x, ldx, nullptr, 0, lanes_per_head, c.slabs, c.its, att);
+      }, elr, shifted, bf);
+    };
+    const int lph32 = static_cast<int>((F / heads) / 4);
+    const bool lean = tuning().att_lean && elr && F == 128 && heads == 8 && lean32_ok(n_cols, ldx, xe) &&
+                      lean32_ok(n_cols, ldb, 4u);
+    if (lean) {
+      const uint32_t rb = static_cast<uint32_t>(ldx * xe), bbytes = static_cast<uint32_t>(ldb * 4);
+      // single-item rows are common only when few blocks cut the rows (low degree, B <= 2); above
+      // that the row_ptr reads at every item's end cost more than the rare direct writes save
+      const bool direct = (tuning().att_direct == 2 || (tuning().att_direct == 1 && blocks <= 2)) && ldy % 4 == 0 &&
+                          aligned(y, 16);
+      skip_single = direct;
+      const int64_t* rp = direct ? c.v.row_ptr : nullptr;
+      with_bools([&](auto SH, auto BF) {  // NT bit 2: non-temporal slab stores; shift is NULL unless shifted
+        k_att_h32<2, SH(), BF()><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, a_dst, lda, b_src, bbytes, c.slabs,
+                                                           c.its, rp, normalize, y, ldy, sums, sf_out, shift);
+      }, shifted, bf);
+    } else if (F == 128 && (F / heads) % 4 == 0 && lph32 >= 1 && 32 % lph32 == 0) {
+      seg4(IC<4>{}, IC<8>{}, IC<32>{}, c.g2h, lph32);
+    } else if (vq == 4) {
+      seg4(IC<4>{}, IC<4>{}, IC<16>{}, c.g4, lph);
+    } else {
+      seg4(IC<16>{}, IC<2>{}, IC<16>{}, c.g4, lph);
+    }
+    GTA_LAUNCHED("k_agg_seg4<att>");
   }
-  const dim3 g3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
   const int H = static_cast<int>(heads);
-  if (F == 64) k_seg_reduce_att<1><<<g3, blk, 0, s>>>(n_rows, slabs, H, normalize, y, ldy, sums, ri, 0, sf_out);
-  else if (F == 128)
-    k_seg_reduce_att<2><<<g3, blk, 0, s>>>(n_rows, slabs, H, normalize, y, ldy, sums, ri, skip_single, sf_out);
-  else k_seg_reduce_att<4><<<g3, blk, 0, s>>>(n_rows, slabs, H, normalize, y, ldy, sums, ri, 0, sf_out);
+  launch_seg_reduce(static_cast<int>(F / 64), [&](auto V) {  // skip_single is set at F = 128 only
+    k_seg_reduce_att<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, H, normalize, y, ldy, sums, c.ri, skip_single, sf_out);
+  });
   GTA_LAUNCHED("k_seg_reduce_att");
   return GTA_OK;
 }
