@@ -1985,27 +1985,45 @@ k_seg_reduce_att(int64_t n_rows, const float* __restrict__ slabs, int H, int nor
 // Light rows merge blocks (row_edges > 0): a row of deg edges uses blocks of
 // m = pow2 >= row_edges * B / deg fine blocks (m <= B), so its items still average
 // ~row_edges edges instead of deg / B -- each item costs a start-up and a 512-B
-// partial written and re-read, whatever its length.  A merged block is scheduled at
-// its first fine block's position.
+// partial written and re-read, whatever its length.
+// Item order (knob seg_class_major, default 1): the rows of one merge factor m = 2^c are a
+// degree class c; the classes run one after the other, m = 1 (the heaviest rows) first, and a
+// class's items are numbered merged-block-major over its own ceil(B / m) merged blocks, so
+// the waves in flight gather from one slice of that class's width.  With 0 -- the order of
+// every plan before the classes -- all rows are one class numbered fine-block-major, a merged
+// block at its first fine block's position.  Partial grouping and each row's list are the
+// same either way: the item order changes no bit of any result.
 // layout (host-computable offsets first, then the item arrays):
 //   int64 hdr[16] {B, bsize, n_rows, unsorted_flag, n_items, item_edges, max_items, row_items byte offset,
-//                  row_edges}
-//   int32 perm[n_rows]             rows, heaviest degree bucket first
+//                  row_edges, class_major}
+//   int32 perm[n_rows]             rows, class-major, heaviest degree bucket first inside a class
 //   int32 seg[n_rows*(B+1)]        per-row segment offsets
-//   int32 bucket[64]               (count, offset) per degree bucket
+//   int32 bucket[2*256]            (count, offset) per (class, degree bucket) key
+//   int32 cls[256]                 class table (kCls* offsets) and the first item id of every group
 //   int64 row_ptr[n_rows+1]        exclusive scan of items per row
-//   int32 cnt[n_rows*B]            items per (block, perm position), scanned in place to item offsets
-//   SegItem items[max_items]       block-major
+//   int32 cnt[n_rows*B]            items per (class, merged block, position in the class), scanned in
+//                                  place to item offsets; sum_c ceil(B / m_c) * n_c <= n_rows * B used
+//   SegItem items[max_items]       class-major, block-major inside a class, longest first inside a block
 //   int32 row_items[max_items]     item ids of each row, (block, part) order
+constexpr int kMaxCls = 7;       // m = 1, 2, ..., 64 (B <= 63)
+constexpr int kMaxGroups = 128;  // (class, merged block) groups: sum_c ceil(63 / 2^c) = 126
+constexpr int kClsBase = 0;      // [kMaxCls + 1] first cnt entry of the class (the last: entries in use)
+constexpr int kClsRow0 = 8;      // [kMaxCls] first perm position
+constexpr int kClsRows = 16;     // [kMaxCls] rows
+constexpr int kClsStep = 24;     // [kMaxCls] fine blocks per group (m; 1 when not class-major)
+constexpr int kClsGroup0 = 32;   // [kMaxCls + 1] first group (the last: groups in all)
+constexpr int kClsFirst = 48;    // [kMaxGroups + 1] first item id of group g (the last: n_items)
+
 struct BlockedView {
   int64_t* hdr;
   int32_t* perm;
   int32_t* seg;
   int32_t* bucket;
+  int32_t* cls;
   int64_t* row_ptr;
   int32_t* cnt;
   int64_t* scan;  // scan scratch (kScanMaxTiles + 1)
-  int32_t* lhist;  // [2][64][kLenBins]: item-length histogram per block, then placement cursors
+  int32_t* lhist;  // [2][kMaxGroups][kLenBins]: item-length histogram per group, then placement cursors
   SegItem* items;
   int32_t* row_items;
   int32_t* item_slot;  // position of item k in row_items (for the length sort)
@@ -2021,9 +2039,9 @@ constexpr int64_t kScanMaxTiles = 4096;  // plan-build scan (scan_excl): tile su
 constexpr int kLenBins = 257;  // item length keys 256 - min(len, 256): longest first
 
 inline int64_t blocked_fixed_bytes(int64_t n_rows, int B) {
-  return round16(128) + round16(n_rows * 4) + round16(n_rows * (B + 1) * 4) + round16(64 * 4) +
+  return round16(128) + round16(n_rows * 4) + round16(n_rows * (B + 1) * 4) + round16(2 * 256 * 4) + round16(256 * 4) +
          round16((n_rows + 1) * 8) + round16(n_rows * B * 4) + round16((kScanMaxTiles + 1) * 8) +
-         round16(2 * 64 * kLenBins * 4);
+         round16(2 * kMaxGroups * kLenBins * 4);
 }
 
 BlockedView blocked_view(void* base, int64_t n_rows, int B, int64_t max_items) {
@@ -2032,11 +2050,12 @@ BlockedView blocked_view(void* base, int64_t n_rows, int B, int64_t max_items) {
   v.hdr = reinterpret_cast<int64_t*>(p); p += round16(16 * 8);
   v.perm = reinterpret_cast<int32_t*>(p); p += round16(n_rows * 4);
   v.seg = reinterpret_cast<int32_t*>(p); p += round16(n_rows * (B + 1) * 4);
-  v.bucket = reinterpret_cast<int32_t*>(p); p += round16(64 * 4);
+  v.bucket = reinterpret_cast<int32_t*>(p); p += round16(2 * 256 * 4);
+  v.cls = reinterpret_cast<int32_t*>(p); p += round16(256 * 4);
   v.row_ptr = reinterpret_cast<int64_t*>(p); p += round16((n_rows + 1) * 8);
   v.cnt = reinterpret_cast<int32_t*>(p); p += round16(n_rows * B * 4);
   v.scan = reinterpret_cast<int64_t*>(p); p += round16((kScanMaxTiles + 1) * 8);
-  v.lhist = reinterpret_cast<int32_t*>(p); p += round16(2 * 64 * kLenBins * 4);
+  v.lhist = reinterpret_cast<int32_t*>(p); p += round16(2 * kMaxGroups * kLenBins * 4);
   v.items = reinterpret_cast<SegItem*>(p); p += round16(max_items * 16);
   v.row_items = reinterpret_cast<int32_t*>(p); p += round16(max_items * 4);
   v.item_slot = reinterpret_cast<int32_t*>(p); p += round16(max_items * 4);
@@ -2065,12 +2084,17 @@ __device__ __forceinline__ int merge_of(int64_t deg, int B, int64_t row_edges) {
   return m;
 }
 
+// (class, degree bucket) key of a row: class log2(m) when class-major, else one class
+__device__ __forceinline__ int row_key(int64_t deg, int m, int class_major) {
+  return (class_major ? (31 - __clz(m)) * 32 : 0) + deg_bucket(deg);
+}
+
 // one wave per row: lane b (0..B) binary-searches the first edge with col >= b*bsize;
 // all lanes also verify the row's columns are sorted (the segments need it).  Also
 // writes the row's item count (sum over blocks of n_parts) into row_ptr[row].
 __global__ void __launch_bounds__(kBlock)
 k_blocked_seg(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows, int B,
-              int64_t bsize, int64_t item_edges, int64_t row_edges, BlockedView v) {
+              int64_t bsize, int64_t item_edges, int64_t row_edges, int class_major, BlockedView v) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
   if (row >= n_rows) return;
@@ -2098,35 +2122,76 @@ k_blocked_seg(const int64_t* __restrict__ indptr, const int32_t* __restrict__ in
   bool bad = false;
   for (int64_t e = rb + lane; e + 1 < re; e += kWave) bad |= indices[e] > indices[e + 1];
   if (__any(bad) && lane == 0) atomicOr(reinterpret_cast<unsigned long long*>(&v.hdr[3]), 1ull);
-  if (lane == 0) atomicAdd(&v.bucket[deg_bucket(re - rb)], 1);
+  if (lane == 0) atomicAdd(&v.bucket[row_key(re - rb, m, class_major)], 1);
 }
 
-__global__ void k_blocked_scan(BlockedView v) {  // heaviest bucket first
-  if (threadIdx.x == 0) {
-    int run = 0;
+// row offsets per (class, bucket) key -- class m = 1 first, inside a class the heaviest bucket
+// first -- and the class table: rows, first perm position, first cnt entry and first group
+__global__ void k_blocked_scan(BlockedView v, int B, int class_major) {
+  if (threadIdx.x != 0) return;
+  int run = 0, base = 0, group = 0;
+  for (int c = 0; c < kMaxCls; ++c) {
+    const int step = class_major ? 1 << c : 1, nb = (B + step - 1) / step, row0 = run;
     for (int k = 31; k >= 0; --k) {
-      v.bucket[32 + k] = run;
-      run += v.bucket[k];
+      v.bucket[256 + c * 32 + k] = run;
+      run += v.bucket[c * 32 + k];
+    }
+    v.cls[kClsBase + c] = base;
+    v.cls[kClsRow0 + c] = row0;
+    v.cls[kClsRows + c] = run - row0;
+    v.cls[kClsStep + c] = step;
+    v.cls[kClsGroup0 + c] = group;
+    // a class without rows (every class but the first when not class-major) has no groups
+    if (run > row0) {
+      base += nb * (run - row0);
+      group += nb;
     }
   }
+  v.cls[kClsBase + kMaxCls] = base;
+  v.cls[kClsGroup0 + kMaxCls] = group;
 }
 
-__global__ void k_blocked_perm(const int64_t* __restrict__ indptr, int64_t n_rows, BlockedView v) {
+__global__ void k_blocked_perm(const int64_t* __restrict__ indptr, int64_t n_rows, int B, int64_t row_edges,
+                               int class_major, BlockedView v) {
   const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (r >= n_rows) return;
-  const int k = deg_bucket(indptr[r + 1] - indptr[r]);
-  const int pos = atomicAdd(&v.bucket[32 + k], 1);  // order inside a bucket is free: results don't depend on it
+  const int64_t deg = indptr[r + 1] - indptr[r];
+  const int k = row_key(deg, merge_of(deg, B, row_edges), class_major);
+  const int pos = atomicAdd(&v.bucket[256 + k], 1);  // order inside a bucket is free: results don't depend on it
   v.perm[pos] = static_cast<int32_t>(r);
 }
 
-// cnt[k] = items of (block b = k / n_rows, row perm[k % n_rows]): the parts of the row's
-// merged block starting at fine block b, 0 if none starts there
+// cnt entry k -> its class c, group (merged block of the class) j and row; false past the
+// entries in use.  b = first fine block of the group.
+struct CntEntry {
+  int c, j, b;
+  int32_t row;
+};
+
+__device__ __forceinline__ bool cnt_entry(const BlockedView& v, int64_t k, CntEntry& e) {
+  if (k >= v.cls[kClsBase + kMaxCls]) return false;
+  int c = 0;
+  while (c + 1 < kMaxCls && k >= v.cls[kClsBase + c + 1]) ++c;  // empty classes share the next one's base
+  const int64_t off = k - v.cls[kClsBase + c], n = v.cls[kClsRows + c];
+  e.c = c;
+  e.j = static_cast<int>(off / n);
+  e.b = e.j * v.cls[kClsStep + c];
+  e.row = v.perm[v.cls[kClsRow0 + c] + (off - e.j * n)];
+  return true;
+}
+
+// cnt[k] = items of (class, group, row): the parts of the row's merged block starting at fine
+// block b, 0 if none starts there (not class-major: a group is one fine block of all rows)
 __global__ void k_blocked_cnt(int64_t n_rows, int B, int64_t item_edges, int64_t row_edges, BlockedView v) {
   const int64_t k = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (k >= n_rows * B) return;
-  const int b = static_cast<int>(k / n_rows);
-  const int32_t row = v.perm[k - static_cast<int64_t>(b) * n_rows];
-  const int32_t* sg = v.seg + static_cast<int64_t>(row) * (B + 1);
+  CntEntry e;
+  if (!cnt_entry(v, k, e)) {
+    v.cnt[k] = 0;
+    return;
+  }
+  const int b = e.b;
+  const int32_t* sg = v.seg + static_cast<int64_t>(e.row) * (B + 1);
   const int m = merge_of(sg[B], B, row_edges);
   v.cnt[k] = (b % m) ? 0 : static_cast<int32_t>(n_parts(sg[min(b + m, B)] - sg[b], item_edges));
 }
@@ -2235,15 +2300,16 @@ void scan_excl(T* a, int64_t n, int total_at_end, int64_t* total, int64_t* scrat
   k_scan_apply<T><<<dim3(static_cast<unsigned>(nt)), dim3(1024), 0, s>>>(a, n, tile, scratch, nt, total_at_end, total);
 }
 
-// items of (block b, perm position i): near-equal parts of the segment, item ids
+// items of cnt entry k (class, group, row): near-equal parts of the segment, item ids
 // cnt[k] .. cnt[k] + parts - 1; each is also listed under its row, after the row's
 // items of blocks < b
 __global__ void k_blocked_items(const int64_t* __restrict__ indptr, int64_t n_rows, int B, int64_t item_edges,
                                 int64_t row_edges, BlockedView v) {
   const int64_t k = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (k >= n_rows * B) return;
-  const int b = static_cast<int>(k / n_rows);
-  const int32_t row = v.perm[k - static_cast<int64_t>(b) * n_rows];
+  CntEntry e;
+  if (k >= n_rows * B || !cnt_entry(v, k, e)) return;
+  const int b = e.b, group = v.cls[kClsGroup0 + e.c] + e.j;
+  const int32_t row = e.row;
   const int32_t* sg = v.seg + static_cast<int64_t>(row) * (B + 1);
   const int m = merge_of(sg[B], B, row_edges);
   if (b % m) return;
@@ -2261,36 +2327,43 @@ __global__ void k_blocked_items(const int64_t* __restrict__ indptr, int64_t n_ro
     v.items[id0 + j] = it;
     v.row_items[slot0 + j] = static_cast<int32_t>(id0 + j);
     v.item_slot[id0 + j] = static_cast<int32_t>(slot0 + j);
-    atomicAdd(&v.lhist[b * kLenBins + 256 - min(it.len, 256)], 1);
+    atomicAdd(&v.lhist[group * kLenBins + 256 - min(it.len, 256)], 1);
   }
 }
 
-// length sort of each block's items (longest first), so the two half-wave items of a wave
+// length sort of each group's items (longest first), so the two half-wave items of a wave
 // hold about the same number of edges and finish together.  Only item ids move: each row's
 // row_items keep their (block, part) order, so the reduce -- and every result -- is unchanged.
 __device__ __forceinline__ int len_key(int len) { return 256 - min(len, 256); }
 
-__global__ void k_items_len_scan(BlockedView v, int64_t n_rows, int B) {
-  const int b = threadIdx.x;
-  if (b >= B) return;
-  int run = v.cnt[static_cast<int64_t>(b) * n_rows];  // first item id of block b
+// one thread per (class, merged block) group: its first item id (the scanned cnt entry of the
+// group's first row) and the placement cursor of each of its length keys
+__global__ void __launch_bounds__(kMaxGroups) k_items_len_scan(BlockedView v) {
+  const int g = threadIdx.x, groups = v.cls[kClsGroup0 + kMaxCls];
+  if (g == groups) v.cls[kClsFirst + g] = static_cast<int32_t>(v.hdr[4]);
+  if (g >= groups) return;
+  int c = 0;
+  while (c + 1 < kMaxCls && g >= v.cls[kClsGroup0 + c + 1]) ++c;
+  const int64_t k = v.cls[kClsBase + c] + static_cast<int64_t>(g - v.cls[kClsGroup0 + c]) * v.cls[kClsRows + c];
+  int run = v.cnt[k];
+  v.cls[kClsFirst + g] = run;
   for (int key = 0; key < kLenBins; ++key) {
-    const int c = v.lhist[b * kLenBins + key];
-    v.lhist[64 * kLenBins + b * kLenBins + key] = run;
-    run += c;
+    const int n = v.lhist[g * kLenBins + key];
+    v.lhist[kMaxGroups * kLenBins + g * kLenBins + key] = run;
+    run += n;
   }
 }
 
-__global__ void k_items_permute(BlockedView v, int64_t n_rows, int B) {
+__global__ void k_items_permute(BlockedView v) {
   const int64_t id = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (id >= v.hdr[4]) return;
-  int lo = 0, hi = B - 1;  // the block holding item id: last b with first id <= id
+  int lo = 0, hi = v.cls[kClsGroup0 + kMaxCls] - 1;  // the group holding item id: last g with first id <= id
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if (v.cnt[static_cast<int64_t>(mid) * n_rows] <= id) lo = mid; else hi = mid - 1;
+    if (v.cls[kClsFirst + mid] <= id) lo = mid; else hi = mid - 1;
   }
   const SegItem it = v.items[id];
-  const int nid = atomicAdd(&v.lhist[64 * kLenBins + lo * kLenBins + len_key(it.len)], 1);
+  const int nid = atomicAdd(&v.lhist[kMaxGroups * kLenBins + lo * kLenBins + len_key(it.len)], 1);
   v.items_tmp[nid] = it;
   v.row_items[v.item_slot[id]] = nid;
 }
@@ -4473,6 +4546,14 @@ struct Tuning {
                            // 0 off, 4 / 8 = row loads in flight per lane and step (1 = 4)
   int agg_w1 = 1;          // k_aggregate with one weight per edge: 64 per load, broadcast (WM_EDGE1); 0 = WM_HEAD
   int expr_lean = 1;       // k_agg_expr for gta_aggregate_expr at F = 128 / 256 (0: k_aggregate's XM_EX* form)
+  int seg_class_major = 1; // blocked plan build: items numbered degree class by degree class (0: fine-block-major
+                           // over all rows, the order before the classes; same results bit for bit)
+  int seg_fine_pct = 100;  // default blocked plan (caller names neither item_edges nor row_edges): fine blocks =
+                           // min(63, round(blocks * pct / 100)) ...
+  int seg_row_edges = 10;  // ... and its row_edges (light rows merge blocks toward this many edges per item) ...
+                           // (100, 10): the best point of profiles/blocked_classes/sweep_*.jsonl, DESIGN.md 3.1
+  int seg_fine_min = 16;   // ... for requests of at least this many blocks; smaller ones are built as asked
+  int seg_item_edges = 0;  // the default plan's item_edges (0 = the front end's default, 256)
   int seg_phase = 0;       // blocked aggregate: 0 = items + reduce, 1 = items only, 2 = reduce only (bench timing)
   int att_lean = 1;        // k_att_h32 for the fused GAT aggregate at F = 128, 8 heads (0: the generic half-wave form)
   int att_direct = 1;      // k_att_h32: a row's only item writes y itself (1: at B <= 2, 2: always, 0: never)
@@ -4538,6 +4619,11 @@ const Knob* find_knob(const char* key) {
       {"agg_bf16_vw8", &Tuning::agg_bf16_vw8, nullptr},
       {"agg_w1", &Tuning::agg_w1, nullptr},
       {"expr_lean", &Tuning::expr_lean, nullptr},
+      {"seg_class_major", &Tuning::seg_class_major, nullptr},
+      {"seg_fine_pct", &Tuning::seg_fine_pct, nullptr},
+      {"seg_row_edges", &Tuning::seg_row_edges, nullptr},
+      {"seg_fine_min", &Tuning::seg_fine_min, nullptr},
+      {"seg_item_edges", &Tuning::seg_item_edges, nullptr},
       {"seg_phase", &Tuning::seg_phase, nullptr},
       {"att_lean", &Tuning::att_lean, nullptr},
       {"att_direct", &Tuning::att_direct, nullptr},
@@ -5061,16 +5147,18 @@ int gta_aggregate_blocked_plan_build(const int64_t* indptr, const int32_t* indic
   BlockedView v = blocked_view(plan, n_rows, B, mi);
   hipStream_t s = S(stream);
   const int64_t bsize = (n_cols + B - 1) / B;
+  const int class_major = tuning().seg_class_major ? 1 : 0;
   const int64_t hdr[16] = {B, bsize, n_rows, 0, 0, item_edges, mi,
-                           reinterpret_cast<char*>(v.row_items) - static_cast<char*>(plan), row_edges};
+                           reinterpret_cast<char*>(v.row_items) - static_cast<char*>(plan), row_edges, class_major};
   GTA_HIP(hipMemcpyAsync(v.hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
-  GTA_HIP(hipMemsetAsync(v.bucket, 0, 64 * 4, s));
+  GTA_HIP(hipMemsetAsync(v.bucket, 0, 2 * 256 * 4, s));
   k_blocked_seg<<<dim3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s>>>(
-      indptr, indices, n_rows, B, bsize, item_edges, row_edges, v);
+      indptr, indices, n_rows, B, bsize, item_edges, row_edges, class_major, v);
   GTA_LAUNCHED("k_blocked_seg");
-  k_blocked_scan<<<1, 64, 0, s>>>(v);
+  k_blocked_scan<<<1, 64, 0, s>>>(v, B, class_major);
   GTA_LAUNCHED("k_blocked_scan");
-  k_blocked_perm<<<dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0, s>>>(indptr, n_rows, v);
+  k_blocked_perm<<<dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0, s>>>(indptr, n_rows, B, row_edges,
+                                                                                         class_major, v);
   GTA_LAUNCHED("k_blocked_perm");
   scan_excl<int64_t>(v.row_ptr, n_rows, 1, nullptr, v.scan, s);  // items per row -> row_ptr
   GTA_LAUNCHED("scan_excl");
@@ -5079,13 +5167,13 @@ int gta_aggregate_blocked_plan_build(const int64_t* indptr, const int32_t* indic
   GTA_LAUNCHED("k_blocked_cnt");
   scan_excl<int32_t>(v.cnt, n_rows * B, 0, &v.hdr[4], v.scan, s);  // -> first item id, n_items
   GTA_LAUNCHED("scan_excl");
-  GTA_HIP(hipMemsetAsync(v.lhist, 0, 64 * kLenBins * 4, s));
+  GTA_HIP(hipMemsetAsync(v.lhist, 0, kMaxGroups * kLenBins * 4, s));
   k_blocked_items<<<gk, dim3(256), 0, s>>>(indptr, n_rows, B, item_edges, row_edges, v);
   GTA_LAUNCHED("k_blocked_items");
-  if (mi > 0) {  // each block's items longest first (matched half-wave pairs; only item ids move)
-    k_items_len_scan<<<1, 64, 0, s>>>(v, n_rows, B);
+  if (mi > 0) {  // each group's items longest first (matched half-wave pairs; only item ids move)
+    k_items_len_scan<<<1, kMaxGroups, 0, s>>>(v);
     GTA_LAUNCHED("k_items_len_scan");
-    k_items_permute<<<dim3(static_cast<unsigned>((mi + 255) / 256)), dim3(256), 0, s>>>(v, n_rows, B);
+    k_items_permute<<<dim3(static_cast<unsigned>((mi + 255) / 256)), dim3(256), 0, s>>>(v);
     GTA_LAUNCHED("k_items_permute");
     GTA_HIP(hipMemcpyAsync(v.items, v.items_tmp, mi * sizeof(SegItem), hipMemcpyDeviceToDevice, s));
   }

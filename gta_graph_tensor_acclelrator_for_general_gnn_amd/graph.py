@@ -79,12 +79,14 @@ class Graph:
     def blocked_plan(self, blocks=32, item_edges=None, row_edges=None):
         """Cached column-blocked plan (segment table over `blocks` source-column blocks, work items
         of <= item_edges edges, light rows' blocks merged toward row_edges edges per item; None =
-        the ops.BlockedPlan defaults)."""
+        the ops.BlockedPlan defaults).  With neither named, the default plan: a request of 16 or
+        more blocks is built over finer blocks that light rows merge back (BlockedPlan.resolve);
+        its key then carries the fine count, apart from a plan asked for by name."""
         from . import ops
-        key = ("blocked", blocks, int(item_edges or ops.BlockedPlan.ITEM_EDGES),
-               int(ops.BlockedPlan.ROW_EDGES if row_edges is None else row_edges))
+        fine, ie, re_ = ops.BlockedPlan.resolve(blocks, item_edges, row_edges)
+        key = ("blocked", blocks, ie, re_) + ((fine,) if fine != blocks else ())
         if key not in self._plans:
-            self._plans[key] = ops.BlockedPlan(self, blocks, key[2], key[3])
+            self._plans[key] = ops.BlockedPlan(self, blocks, item_edges, row_edges)
         return self._plans[key]
 
     def numpy(self):

@@ -336,17 +336,43 @@ class BlockedPlan:
     """Column-blocked aggregate plan (gta_aggregate_blocked_plan_build): per-row segment table over
     B source-column blocks, heaviest-first row order, and the work items -- every (block, row)
     segment cut into parts of <= item_edges edges -- with each row's item list for the ordered
-    reduce."""
+    reduce.
+
+    A caller that names item_edges or row_edges gets exactly those over the `blocks` it asked
+    for.  The default plan (neither named) of a request of >= seg_fine_min blocks is built
+    over min(63, round(blocks * seg_fine_pct / 100)) fine blocks with row_edges = seg_row_edges
+    (libgta knobs; BlockedPlan.resolve): light rows merge the fine blocks back, degree class by
+    degree class.  `blocks` is the count the plan was built with -- the one every native call
+    that takes the plan needs -- and `requested` what the caller asked for."""
 
     ITEM_EDGES = 256  # default part length (profiles/r01_item_sweep.json)
-    ROW_EDGES = 0     # default merge target for light rows (0 = off)
+    ROW_EDGES = 0     # merge target for light rows of a plan whose caller names item_edges only (0 = off)
+    MAX_BLOCKS = 63
+
+    @staticmethod
+    def resolve(blocks, item_edges=None, row_edges=None, knobs=None):
+        """(fine blocks, item_edges, row_edges) of the plan blocked_plan(blocks, item_edges, row_edges)
+        builds.  knobs: (seg_fine_pct, seg_row_edges, seg_fine_min); None = the calling thread's
+        values in libgta.  Requests below seg_fine_min blocks (the 60 MB column half of a 2-D tile
+        asks for 10) keep their blocks and row_edges 0."""
+        blocks = int(blocks)
+        named = (blocks, int(item_edges or BlockedPlan.ITEM_EDGES),
+                 int(BlockedPlan.ROW_EDGES if row_edges is None else row_edges))
+        if item_edges is not None or row_edges is not None:
+            return named
+        if knobs is None:
+            knobs = tuple(get_debug(k) for k in ("seg_fine_pct", "seg_row_edges", "seg_fine_min", "seg_item_edges"))
+        pct, re_, least, ie = (tuple(knobs) + (0,))[:4]  # seg_item_edges: the sweeps' item length (0 = ITEM_EDGES)
+        if blocks < least:
+            return named
+        fine = min(BlockedPlan.MAX_BLOCKS, max(1, int(math.floor(blocks * pct / 100.0 + 0.5))))
+        return fine, int(ie or BlockedPlan.ITEM_EDGES), max(0, int(re_))
 
     def __init__(self, graph, blocks=32, item_edges=None, row_edges=None):
         _need_gpu(graph.indptr)
         L = _L()
-        self.graph, self.blocks = graph, int(blocks)
-        self.item_edges = int(item_edges or BlockedPlan.ITEM_EDGES)
-        self.row_edges = int(BlockedPlan.ROW_EDGES if row_edges is None else row_edges)
+        self.graph, self.requested = graph, int(blocks)
+        self.blocks, self.item_edges, self.row_edges = BlockedPlan.resolve(blocks, item_edges, row_edges)
         nb = check(L.gta_aggregate_blocked_plan_bytes(graph.n_rows, graph.nnz, self.blocks, self.item_edges),
                    "blocked_plan_bytes")
         self.buf = torch.empty(int(nb), dtype=torch.uint8, device=graph.device)
@@ -397,7 +423,10 @@ class BlockedPlan:
         table, B = 10 for the 60 MB column half of a 2-D grid tile; profiles/r01_blocks_rowmerge_sweep.json,
         r01_shard_b_sweep.json), capped so a row keeps >= 24 edges per block on average (each
         (block, row) item pays a start-up and a partial row written and re-read).
-        Below 4 the single-pass row-chunk kernel is the better choice."""
+        Below 4 the single-pass row-chunk kernel is the better choice.
+        This is the REQUEST: the count a caller passes as `blocks`.  The default plan of such a
+        request may be built over finer blocks that light rows merge back (BlockedPlan.resolve,
+        knobs seg_fine_pct / seg_row_edges; DESIGN §3.1 has the sweep that set them)."""
         table_mb = graph.n_cols * F * elem / 1e6
         avg_deg = graph.nnz / max(1, graph.n_rows)
         return int(max(1, min(24, round(table_mb / 6.0), avg_deg // 24)))

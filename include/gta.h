@@ -269,13 +269,20 @@ int64_t gta_aggregate_workspace_bytes(int64_t n_rows, int64_t nnz, int64_t chunk
  * most blocks), so its items still hold ~row_edges edges; 0 = every row uses
  * all blocks.  Only the plan build takes it (any value keeps y within fp32
  * rounding; the sum order per row is fixed by the plan).
+ * The rows of one m are a degree class: the items are numbered class by class,
+ * m = 1 first, merged-block-major inside a class and longest first inside a
+ * merged block (knob seg_class_major, read by the plan build; 0 numbers all rows
+ * fine-block-major, a merged block at its first fine block).  The item order
+ * changes no bit of any result.  The knobs seg_fine_pct, seg_row_edges,
+ * seg_fine_min and seg_item_edges are only stored here: a front end reads them
+ * to turn a requested block count into the default plan's arguments.
  * plan, workspace and launch must use the same (nnz, blocks, item_edges). */
 int64_t gta_aggregate_blocked_plan_bytes(int64_t n_rows, int64_t nnz, int64_t blocks, int64_t item_edges);
 int gta_aggregate_blocked_plan_build(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
                                      int64_t nnz, int64_t blocks, int64_t item_edges, int64_t row_edges,
                                      void* plan, int64_t plan_bytes, void* stream);
 /* workspace >= gta_aggregate_blocked_workspace_bytes (may be NULL only when nnz == 0):
- * one launch over the plan's items in block-major order, item k writing partial row
+ * one launch over the plan's items in the plan's order, item k writing partial row
  * k, then an ordered reduce summing each row's items in (block, part) order. */
 int64_t gta_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, int64_t blocks, int64_t F,
                                               int64_t item_edges);
