@@ -2870,7 +2870,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // SF epilogue of the MFMA GEMMs applied to the whole accumulator tile in place, the switch on sf
 // OUTSIDE the element loops.  With sf_apply per element each of the FR x NT x 4 store sites held
-// its own switch over every SF body: k_mm_ring<8, 8, 2> compiled to 147 KB, and an epilogue run
+// its own switch over every SF body: the 8-deep k_mm_ring<8, 8, 2> of that time (since removed)
+// compiled to 147 KB, and an epilogue run
 // walked ~100 KB of cold instruction cache (each new lane of code an L2 round trip), a fixed
 // ~10 us per launch that a 9-stage split-K block could not hide.  Here the no-SF path is one branch.
 template <int FR, int NT>
@@ -3025,6 +3026,101 @@ k_mm_bf16(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row
       }
 }
 
+// ---- pieces shared by the MFMA UPDATE kernels (k_mm_rows, k_mm_ring, k_mm_wave, k_mm_ring_bf, k_mlp_bf) ----
+// An MFMA 16x16 tile leaves lane (g, r16 = 4q + p) with C[4g + r][4q + p], r = 0..3.  A 4x4
+// transpose inside each lane quad (DPP swaps of lane bit 0, then bit 1) turns that into
+// C[4g + p][4q + r]: four consecutive columns of one row, one 16-B store instead of four dwords.
+__device__ __forceinline__ void quad_transpose(float (&v)[4], int p) {
+#pragma unroll
+  for (int m2 = 0; m2 < 2; ++m2) {  // bit 0: registers (2m2, 2m2+1) across lanes (p, p^1)
+    const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2]), 0xB1, 0xF, 0xF, false));
+    const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2 + 1]), 0xB1, 0xF, 0xF, false));
+    if (p & 1) v[2 * m2] = sb; else v[2 * m2 + 1] = sa;
+  }
+#pragma unroll
+  for (int m2 = 0; m2 < 2; ++m2) {  // bit 1: registers (m2, m2+2) across lanes (p, p^2)
+    const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2]), 0x4E, 0xF, 0xF, false));
+    const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2 + 2]), 0x4E, 0xF, 0xF, false));
+    if (p & 2) v[m2] = sb; else v[m2 + 2] = sa;
+  }
+}
+
+// The accumulators of a (16 FR) x (16 NT) wave tile, rows from mw and columns from n0, out (the SF
+// already applied: sf_tile): quad-transposed 16-B row stores when out rows are 16-B aligned
+// (vstore), per element at a column tail and otherwise.  Rows past M and columns past N are skipped.
+template <int FR, int NT>
+__device__ __forceinline__ void store_tile(const f32x4 (&acc)[FR][NT], float* __restrict__ out, int64_t ldo, int64_t M,
+                                           int N, int64_t mw, int n0, int lane, bool vstore) {
+  const int g = lane >> 4, r16 = lane & 15;
+  if (vstore) {
+    const int p = r16 & 3, q = r16 >> 2;
+#pragma unroll
+    for (int i = 0; i < FR; ++i)
+#pragma unroll
+      for (int c = 0; c < NT; ++c) {
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = acc[i][c][r];
+        quad_transpose(v, p);
+        const int64_t m = mw + 16 * i + 4 * g + p;
+        const int n = n0 + 16 * c + 4 * q;
+        if (m < M) {
+          if (n + 3 < N) {
+            *reinterpret_cast<float4*>(out + m * ldo + n) = make_float4(v[0], v[1], v[2], v[3]);
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (n + r < N) out[m * ldo + n + r] = v[r];
+          }
+        }
+      }
+  } else {
+#pragma unroll
+    for (int i = 0; i < FR; ++i)
+#pragma unroll
+      for (int c = 0; c < NT; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t m = mw + 16 * i + 4 * g + r;
+          const int n = n0 + 16 * c + r16;
+          if (m < M && n < N) out[m * ldo + n] = acc[i][c][r];
+        }
+  }
+}
+
+template <int FR, int NT>
+__device__ __forceinline__ void zero_tile(f32x4 (&acc)[FR][NT]) {
+#pragma unroll
+  for (int i = 0; i < FR; ++i)
+#pragma unroll
+    for (int c = 0; c < NT; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// One 16-k fp32 step on fragments in registers: FR x NT x 4 v_mfma_f32_16x16x4_f32.  jj outermost:
+// each of the FR x NT accumulators is touched once per FR * NT MFMAs; per accumulator the k order
+// is k_mm_rows' (bitwise equal to it).
+template <int FR, int NT>
+__device__ __forceinline__ void mma_f32_step(f32x4 (&acc)[FR][NT], const f32x4 (&a4)[FR], const f32x4 (&b4)[NT]) {
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+    for (int c = 0; c < NT; ++c)
+#pragma unroll
+      for (int i = 0; i < FR; ++i)
+        acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[i][jj], b4[c][jj], acc[i][c], 0, 0, 0);
+}
+
+// Split K: block row y contracts k in [y * kslice, (y + 1) * kslice) into its own partial
+// out + y * oslice; k_mm_slices_sum adds the slices in order.
+template <typename PX, typename PW, typename PO>
+__device__ __forceinline__ void split_k_slice(PX& x, PW& wt, PO& out, int& K, int64_t kslice, int64_t oslice) {
+  const int64_t kb = static_cast<int64_t>(blockIdx.y) * kslice;
+  x += kb;
+  wt += kb;
+  K = static_cast<int>(min<int64_t>(kslice, K - kb));
+  out += static_cast<int64_t>(blockIdx.y) * oslice;
+}
+
 // Row-streaming UPDATE for the skinny shapes of GNN layers (M = nodes or edges,
 // K and N at most a few hundred).  A block owns BN = 16*NT output columns (all of
 // N up to 128, so X is read from HBM once) and walks 128-row groups g, g+grid, ...
@@ -3042,14 +3138,8 @@ __global__ void __launch_bounds__(kBlock, PF ? 4 : 1)
 k_mm_rows(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row_idx, int64_t M, int K,
           const WT* __restrict__ wt, int64_t ldwt, int N, int sf, float* __restrict__ out, int64_t ldo,
           int64_t kslice = 0, int64_t oslice = 0, int vec_store = 0) {
-  // split K (kslice > 0): block row y contracts k in [y * kslice, (y + 1) * kslice) into its own
-  // partial out + y * oslice (no SF); k_mm_slices_sum adds the slices in order
-  if (kslice > 0) {
-    const int64_t kb = static_cast<int64_t>(blockIdx.y) * kslice;
-    x += kb;
-    wt += kb;
-    K = static_cast<int>(min<int64_t>(kslice, K - kb));
-    out += static_cast<int64_t>(blockIdx.y) * oslice;
+  if (kslice > 0) {  // split K: a partial sum takes no SF
+    split_k_slice(x, wt, out, K, kslice, oslice);
     sf = GTA_SF_NONE;
   }
   constexpr bool BF = sizeof(WT) == 2;
@@ -3114,10 +3204,7 @@ k_mm_rows(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row
       ap[i] = x + src * ldx;
     }
     f32x4 acc[2][NT];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int c = 0; c < NT; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_tile(acc);
 
     for (int kc = 0; kc < K; kc += KC) {
       if (!one_chunk) {
@@ -3147,11 +3234,8 @@ k_mm_rows(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row
               }
               continue;
             }
-          }
-          if (avec && aok[i] && k0 + AV <= K) {
-            if constexpr (sizeof(TA) == 4) {
-              // handled above
-            } else {
+          } else {
+            if (avec && aok[i] && k0 + AV <= K) {  // bf16 x: one 16-B piece of 8 values
               const uint4 u = *reinterpret_cast<const uint4*>(ap[i] + k0);
               const uint32_t uw[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
@@ -3159,17 +3243,17 @@ k_mm_rows(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row
                 av[i][2 * q] = __uint_as_float(uw[q] << 16);
                 av[i][2 * q + 1] = __uint_as_float(uw[q] & 0xffff0000u);
               }
+              continue;
             }
-          } else {
+          }
 #pragma unroll
-            for (int q = 0; q < AV; ++q) {
-              float v = 0.f;
-              if (aok[i] && k0 + q < K) {
-                if constexpr (sizeof(TA) == 4) v = reinterpret_cast<const float*>(ap[i])[k0 + q];
-                else v = __uint_as_float(static_cast<uint32_t>(reinterpret_cast<const uint16_t*>(ap[i])[k0 + q]) << 16);
-              }
-              av[i][q] = v;
+          for (int q = 0; q < AV; ++q) {  // unaligned rows, a bf16 piece across K, rows past M: per element
+            float v = 0.f;
+            if (aok[i] && k0 + q < K) {
+              if constexpr (sizeof(TA) == 4) v = reinterpret_cast<const float*>(ap[i])[k0 + q];
+              else v = __uint_as_float(static_cast<uint32_t>(reinterpret_cast<const uint16_t*>(ap[i])[k0 + q]) << 16);
             }
+            av[i][q] = v;
           }
         }
       };
@@ -3215,6 +3299,8 @@ k_mm_rows(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row
       }
       if (!one_chunk) __syncthreads();
     }
+    // store_tile's text, written out: through the helper k_mm_rows<float, float, 8, true> gained
+    // 8 B of scratch and 15 spill instructions; this is the code the kernel had
     sf_tile(sf, acc);
     if (vstore) {
       // lane (g, r16 = 4q + p) holds C[4g + r][4q + p], r = 0..3; a 4x4 transpose inside each
@@ -3267,61 +3353,6 @@ k_mm_rows(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row
   }
 }
 
-// The accumulator tile of a (16 FR) x (16 NT) wave tile out as k_mm_rows / k_mm_ring store it:
-// the SF applied, then quad-transposed 16-B row stores (two DPP swaps per quad turn the lane's 4
-// rows of one column into 4 columns of one row) when out rows are 16-B aligned, else per element.
-template <int FR, int NT>
-__device__ __forceinline__ void store_tile(f32x4 (&acc)[FR][NT], int sf, float* __restrict__ out, int64_t ldo,
-                                           int64_t M, int N, int64_t mw, int n0, int lane, bool vstore) {
-  const int g = lane >> 4, r16 = lane & 15;
-  sf_tile(sf, acc);
-  if (vstore) {
-    const int p = r16 & 3, q = r16 >> 2;
-#pragma unroll
-    for (int i = 0; i < FR; ++i)
-#pragma unroll
-      for (int c = 0; c < NT; ++c) {
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[i][c][r];
-#pragma unroll
-        for (int m2 = 0; m2 < 2; ++m2) {
-          const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2]), 0xB1, 0xF, 0xF, false));
-          const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2 + 1]), 0xB1, 0xF, 0xF, false));
-          if (p & 1) v[2 * m2] = sb; else v[2 * m2 + 1] = sa;
-        }
-#pragma unroll
-        for (int m2 = 0; m2 < 2; ++m2) {
-          const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2]), 0x4E, 0xF, 0xF, false));
-          const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2 + 2]), 0x4E, 0xF, 0xF, false));
-          if (p & 2) v[m2] = sb; else v[m2 + 2] = sa;
-        }
-        const int64_t m = mw + 16 * i + 4 * g + p;
-        const int n = n0 + 16 * c + 4 * q;
-        if (m < M) {
-          if (n + 3 < N) {
-            *reinterpret_cast<float4*>(out + m * ldo + n) = make_float4(v[0], v[1], v[2], v[3]);
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (n + r < N) out[m * ldo + n + r] = v[r];
-          }
-        }
-      }
-  } else {
-#pragma unroll
-    for (int i = 0; i < FR; ++i)
-#pragma unroll
-      for (int c = 0; c < NT; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t m = mw + 16 * i + 4 * g + r;
-          const int n = n0 + 16 * c + r16;
-          if (m < M && n < N) out[m * ldo + n] = acc[i][c][r];
-        }
-  }
-}
-
 // fp32 UPDATE on MFMA with an LDS-DMA ring (the plain fp32 GEMM of GCN/GAT/SAGE layers,
 // `template/ISA_defination.yaml:1-31` j,ij->i; LOAD_W `code/interpreter.py:335-343`).
 // Why not k_mm_rows: there each K chunk of W is staged synchronously (stage, barrier, compute)
@@ -3342,9 +3373,9 @@ __device__ __forceinline__ void store_tile(f32x4 (&acc)[FR][NT], int sf, float* 
 // past N read clamped rows and are not stored.  Same per-lane k order and fma chain as
 // k_mm_rows: results bitwise equal to it.  LDS: D x (4 FR + NT) KiB.
 //   D = 3: the persistent many-group form (48 KiB at FR = 2, N = 128: 3 blocks per CU);
-//   D = 4: two blocks per CU; D = 8: one block per CU, seven stages in flight -- the split-K
-//   form (one (row group, K slice) per block, every block resident at once) and grids of at most
-//   one block per CU, where a 3-deep ring leaves each stage waiting out an HBM round trip.
+//   D = 4: the split-K form (one (row group, K slice) per block, three blocks per CU at FR = 1).
+//   Deeper rings at fewer blocks per CU measured slower on every shape
+//   (profiles/r03/mm_depth_sweep.log, mm_cora_epilogue.log) and are not built.
 // Split K (kslice > 0): block row y contracts k in [y * kslice, +kslice) into output slice y.
 // generic -> LDS address space, and the 32-bit LDS byte address (macros: a __device__ helper
 // taking or returning address-space-3 pointers keeps hipcc from emitting a template kernel's host stub)
@@ -3353,15 +3384,6 @@ __device__ __forceinline__ void store_tile(f32x4 (&acc)[FR][NT], int sf, float* 
 template <int OFF>
 __device__ __forceinline__ void ds_read16(f32x4& v, uint32_t a) {  // result valid after an lgkmcnt wait
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(OFF));
-}
-__device__ __forceinline__ void ds_read16_idx(f32x4& v, uint32_t a, int c) {  // c: 1 KiB fragment index < 16 (unrolled)
-  switch (c) {
-#define GTA_DSR(C_) case C_: ds_read16<(C_) * 1024>(v, a); break;
-    GTA_DSR(0) GTA_DSR(1) GTA_DSR(2) GTA_DSR(3) GTA_DSR(4) GTA_DSR(5) GTA_DSR(6) GTA_DSR(7)
-    GTA_DSR(8) GTA_DSR(9) GTA_DSR(10) GTA_DSR(11) GTA_DSR(12) GTA_DSR(13) GTA_DSR(14)
-#undef GTA_DSR
-    default: ds_read16<15 * 1024>(v, a); break;
-  }
 }
 __device__ __forceinline__ void ds_read16_kib(f32x4& v, uint32_t a, int c) {  // c: KiB offset < 64 (unrolled)
   switch (c) {
@@ -3391,6 +3413,123 @@ __device__ __forceinline__ void vm_wait_stages(int n) {
 // blocks per CU the ring's LDS allows (<= 4), the __launch_bounds__ waves per SIMD
 constexpr int ring_blocks(int NT, int D, int FR) {
   return (160 / (D * (4 * FR + NT))) > 4 ? 4 : (160 / (D * (4 * FR + NT)));
+}
+
+// The persistent ring schedule, as k_mm_ring_bf runs it (k_mm_ring below keeps the same schedule
+// written out: with these shared pieces its 64-row forms measured 5 - 11 % slower, DESIGN.md 3.8;
+// until that cause is found RingSched and ring_run have this one caller).  A block's row groups
+// are grp0, grp0 + gstep, ...; the ring runs on across them (stage t = (group j, step s) of S per
+// group), so the next group's first stages land while this group finishes and no block pays a
+// prologue after the first.  (j, s, slot) is the next stage to DMA as (group, stage in group, ring
+// slot), advanced by one per issue: no 64-bit division per stage (its ~150 scalar instructions
+// per stage were measurable).
+template <int D>
+struct RingSched {
+  int64_t grp0, gstep, my_groups, T;  // T: this block's stages in all
+  int S;
+  int64_t j = 0;
+  int s = 0, slot = 0;
+  __device__ __forceinline__ RingSched(int ncb, int64_t n_groups, int S_)
+      : grp0(blockIdx.x / ncb), gstep(gridDim.x / ncb),
+        my_groups(grp0 < n_groups ? (n_groups - grp0 + gstep - 1) / gstep : 0), T(my_groups * S_), S(S_) {}
+  __device__ __forceinline__ int64_t first_row(int64_t jj, int GR) const { return (grp0 + jj * gstep) * GR; }
+  // one stage on; a kernel that sees j change recomputes its source rows (it compares j with the
+  // group it holds rows of: a "new group" flag handed back from here cost registers and scratch)
+  __device__ __forceinline__ void advance() {
+    slot = slot + 1 == D ? 0 : slot + 1;
+    if (++s == S) {
+      s = 0;
+      ++j;
+    }
+  }
+};
+
+// The ring's loop over this block's groups and stages.  issue() DMAs the stage at rs' cursor and
+// advances it; stage(slot, s) reads stage s of the current group from its slot and runs its MFMA
+// step; tail(j) adds a K tail the ring does not carry; epilogue(j) puts the group's rows out.
+// Per stage: stage t landed (stages t+1 .. t+D-2 may stay in flight), every wave done with the
+// slot about to be refilled (read at t-1), then the DMA of stage t + D - 1.
+template <int PER_STAGE, int D, int FR, int NT, class Issue, class Stage, class Tail, class Epilogue>
+__device__ __forceinline__ void ring_run(const RingSched<D>& rs, f32x4 (&acc)[FR][NT], Issue&& issue, Stage&& stage,
+                                         Tail&& tail, Epilogue&& epilogue) {
+  const int64_t T = rs.T, my_groups = rs.my_groups;
+  const int S = rs.S;
+  zero_tile(acc);  // (a slice shorter than one stage has no stages: T = 0, the tail does it all)
+#pragma unroll
+  for (int p = 0; p + 1 < D; ++p)
+    if (p < T) issue();
+  int64_t t = 0;
+  int slot = 0;  // ring slot of stage t
+  for (int64_t j = 0; j < my_groups; ++j) {
+    for (int s = 0; s < S; ++s, ++t, slot = slot + 1 == D ? 0 : slot + 1) {
+      const int64_t later = T - 1 - t;
+      vm_wait_stages<PER_STAGE>(static_cast<int>(later < D - 2 ? later : D - 2));
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (t + D - 1 < T) issue();
+      stage(slot, s);
+    }
+    // the group's last stage is done: its K tail, its rows out, the next group's sums
+    tail(j);
+    epilogue(j);
+    zero_tile(acc);
+    // the counted waits above assume only ring DMA is outstanding; stores may retire out of order
+    // with the loads, so drain them here (the next group's first stages have had a step to land)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+}
+
+// One 32-k bf16 step against W^T resident in LDS (stage_wt_frags' layout): the NT column fragments
+// first_frag + c * frag_stride, in KiB from lds_addr (which carries the lane's 16-B offset), read,
+// waited for and pinned, then NT x FR v_mfma_f32_16x16x32_bf16.  The A fragments a (16 B each: bf16x8,
+// or the raw f32x4 of an LDS read issued just before the call) are pinned under the same wait and
+// read as bf16x8 only after it.
+template <int FR, int NT, typename A>
+__device__ __forceinline__ void mma_bf_resident(f32x4 (&acc)[FR][NT], A (&a)[FR], uint32_t lds_addr, int first_frag,
+                                                int frag_stride) {
+  static_assert(sizeof(A) == 16, "one 16-B MFMA operand per fragment");
+  f32x4 b4[NT];
+#pragma unroll
+  for (int c = 0; c < NT; ++c) ds_read16_kib(b4[c], lds_addr, first_frag + c * frag_stride);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < FR; ++i) asm volatile("" : "+v"(a[i]));
+#pragma unroll
+  for (int c = 0; c < NT; ++c) asm volatile("" : "+v"(b4[c]));
+#pragma unroll
+  for (int c = 0; c < NT; ++c) {
+    const bf16x8 b8 = __builtin_bit_cast(bf16x8, b4[c]);
+#pragma unroll
+    for (int i = 0; i < FR; ++i)
+      acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[i]), b8, acc[i][c], 0, 0, 0);
+  }
+}
+
+// W^T [N, K] bf16 into LDS in MFMA fragment layout, by every thread of the block (the caller's
+// __syncthreads() publishes it): fragment (c, s) of NT x SB at dst + (c * SB + s) KiB holds lane L's
+// 8 bf16 of row n0 + 16c + (L & 15), k = 32s + 8(L >> 4) .. +7, zeros past K and N.  A 16-B load
+// where the piece is aligned and inside K, per element otherwise.
+template <int NT, int SB>
+__device__ __forceinline__ void stage_wt_frags(char* dst, const uint16_t* __restrict__ wt, int64_t ldwt, int n0, int N,
+                                               int K) {
+  for (int e = threadIdx.x; e < NT * SB * kWave; e += kBlock) {
+    const int L = e & (kWave - 1), f = e >> 6, c = f / SB, s = f - c * SB;
+    const int n = n0 + 16 * c + (L & 15), k = 32 * s + 8 * (L >> 4);
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (n < N && k < K) {
+      const uint16_t* p = wt + static_cast<int64_t>(n) * ldwt + k;
+      if (k + 8 <= K && aligned(p, 16)) {
+        v = *reinterpret_cast<const uint4*>(p);
+      } else {
+        uint16_t tmp[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) tmp[q] = (k + q < K) ? p[q] : static_cast<uint16_t>(0);
+        v = *reinterpret_cast<const uint4*>(tmp);
+      }
+    }
+    *reinterpret_cast<uint4*>(dst + f * 1024 + L * 16) = v;
+  }
 }
 
 template <int NT, int D = 3, int FR = 2>
@@ -3594,9 +3733,9 @@ k_mm_ring(const float* __restrict__ x, int64_t ldx, const int32_t* __restrict__ 
     const uint32_t sb = GTA_LDS_ADDR(lds + slot * STAGE + A_BYTES) + rdoff;
     f32x4 a4[FR], b4[NT];
 #pragma unroll
-    for (int i = 0; i < FR; ++i) ds_read16_idx(a4[i], sa, i);
+    for (int i = 0; i < FR; ++i) ds_read16_kib(a4[i], sa, i);
 #pragma unroll
-    for (int c = 0; c < NT; ++c) ds_read16_idx(b4[c], sb, c);
+    for (int c = 0; c < NT; ++c) ds_read16_kib(b4[c], sb, c);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
     for (int i = 0; i < FR; ++i) asm volatile("" : "+v"(a4[i]));
@@ -3668,10 +3807,7 @@ k_mm_wave(const float* __restrict__ x, int64_t ldx, int64_t M, int K, const floa
 #pragma unroll
     for (int c = 0; c < NT; ++c) bo[c] = static_cast<uint32_t>((static_cast<int64_t>(min(n0 + 16 * c + r16, N - 1)) * ldwt + 4 * g) * 4);
     f32x4 acc[FR][NT];
-#pragma unroll
-    for (int i = 0; i < FR; ++i)
-#pragma unroll
-      for (int c = 0; c < NT; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_tile(acc);
     f32x4 a0[FR], a1[FR], a2[FR], a3[FR], b0[NT], b1[NT];
     auto load_a = [&](f32x4 (&a)[FR], int s) __attribute__((always_inline)) {
       const int so = min(s, SF - 1) * 64;
@@ -3705,13 +3841,7 @@ k_mm_wave(const float* __restrict__ x, int64_t ldx, int64_t M, int K, const floa
           for (int c = 0; c < NT; ++c) bc[c][e] = past ? 0.f : bc[c][e];
         }
       }
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-        for (int c = 0; c < NT; ++c)
-#pragma unroll
-          for (int i = 0; i < FR; ++i)
-            acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[i][jj], bc[c][jj], acc[i][c], 0, 0, 0);
+      mma_f32_step(acc, ac, bc);
     };
     // issue order A(0), A(1), B(0), A(2): after B(t) come A(t + 2), B(t + 1), A(t + 3) for every t
     load_a(a0, 0);
@@ -3745,7 +3875,8 @@ k_mm_wave(const float* __restrict__ x, int64_t ldx, int64_t M, int K, const floa
     for (int i = 0; i < FR; ++i) asm volatile("" ::"v"(a0[i]), "v"(a1[i]), "v"(a2[i]), "v"(a3[i]));
 #pragma unroll
     for (int c = 0; c < NT; ++c) asm volatile("" ::"v"(b0[c]), "v"(b1[c]));
-    store_tile(acc, sf, out, ldo, M, N, mw, n0, lane, vstore);
+    sf_tile(sf, acc);
+    store_tile(acc, out, ldo, M, N, mw, n0, lane, vstore);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 }
@@ -3784,36 +3915,15 @@ k_mm_ring_bf(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ 
   const int g = lane >> 4, r16 = lane & 15;
   const int ncb = (N + BN - 1) / BN;
   const int n0 = static_cast<int>(blockIdx.x % ncb) * BN;
-  const int64_t grp0 = blockIdx.x / ncb, gstep = gridDim.x / ncb;
-  const int64_t n_groups = (M + GR - 1) / GR;
-  const int64_t my_groups = grp0 < n_groups ? (n_groups - grp0 + gstep - 1) / gstep : 0;
   // a K tail is one more ring stage when its pieces (4 fp32 / 8 bf16) lie wholly inside or wholly past
   // K (those read the row start and are zeroed after the LDS read); else a masked register step
   const bool ring_tail = (K % KS) != 0 && (K % (PA == 2 ? 4 : 8)) == 0;
   const int S = ring_tail ? (K + KS - 1) / KS : K / KS;
   const int kdead = ring_tail ? K - (S - 1) * KS : KS;  // pieces of the last stage from this k (lane-relative) are past K
-  const int64_t T = my_groups * S;
-  // W^T resident: fragment (c, s) at bres + (c * SB + s) KiB, lane L's 8 bf16 of row n0 + 16c + r16,
-  // k = 32s + 8g .. +7 (zeros past K and N)
-  for (int e = threadIdx.x; e < NT * SB * kWave; e += kBlock) {
-    const int L = e & (kWave - 1), f = e >> 6, c = f / SB, s = f - c * SB;
-    const int n = n0 + 16 * c + (L & 15), k = 32 * s + 8 * (L >> 4);
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (n < N && k < K) {
-      const uint16_t* p = wt + static_cast<int64_t>(n) * ldwt + k;
-      if (k + 8 <= K && aligned(p, 16)) {
-        v = *reinterpret_cast<const uint4*>(p);
-      } else {
-        uint16_t tmp[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) tmp[q] = (k + q < K) ? p[q] : static_cast<uint16_t>(0);
-        v = *reinterpret_cast<const uint4*>(tmp);
-      }
-    }
-    *reinterpret_cast<uint4*>(bres + f * 1024 + L * 16) = v;
-  }
+  RingSched<D> rs(ncb, (M + GR - 1) / GR, S);
+  stage_wt_frags<NT, SB>(bres, wt, ldwt, n0, N, K);
   auto a_row = [&](int64_t j, int i, int sub) __attribute__((always_inline)) -> const TA* {
-    const int64_t m = min<int64_t>((grp0 + j * gstep) * GR + wv * (16 * FR) + 16 * i + sub, M - 1);
+    const int64_t m = min<int64_t>(rs.first_row(j, GR) + wv * (16 * FR) + 16 * i + sub, M - 1);
     return x + (row_idx ? static_cast<int64_t>(row_idx[m]) : m) * ldx;
   };
   // DMA lane map (row-contiguous, as k_mm_ring's): DMA instruction p of a fragment holds rows
@@ -3833,25 +3943,19 @@ k_mm_ring_bf(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ 
     rdoff[p] = static_cast<uint32_t>(r16 * RB + (((PA == 2 ? 2 * g + p : g)) ^ swz(r16)) * 16);
   }
   const TA* asrc[FR][PA];
-  int64_t asrc_j = -1, iss_j = 0;
-  int iss_s = 0, iss_slot = 0;
-  auto issue = [&]() __attribute__((always_inline)) {
-    const int64_t j = iss_j;
-    const int k = iss_s * KS;
-    if (j != asrc_j) {
+  int64_t asrc_j = -1;  // the group asrc holds rows of
+  auto issue = [&]() __attribute__((always_inline)) {  // the DMA of stage rs.(j, s) into rs.slot
+    if (rs.j != asrc_j) {
+      asrc_j = rs.j;
 #pragma unroll
       for (int i = 0; i < FR; ++i)
 #pragma unroll
-        for (int p = 0; p < PA; ++p) asrc[i][p] = a_row(j, i, drow[p]) + doff[p];
-      asrc_j = j;
+        for (int p = 0; p < PA; ++p) asrc[i][p] = a_row(rs.j, i, drow[p]) + doff[p];
     }
-    char* base = lds + iss_slot * STAGE;
-    iss_slot = iss_slot + 1 == D ? 0 : iss_slot + 1;
-    const bool last = ring_tail && iss_s == S - 1;
-    if (++iss_s == S) {
-      iss_s = 0;
-      ++iss_j;
-    }
+    char* base = lds + rs.slot * STAGE;
+    const int k = rs.s * KS;
+    const bool last = ring_tail && rs.s == S - 1;
+    rs.advance();
 #pragma unroll
     for (int i = 0; i < FR; ++i)
 #pragma unroll
@@ -3864,12 +3968,6 @@ k_mm_ring_bf(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ 
       }
   };
   f32x4 acc[FR][NT];
-  auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < FR; ++i)
-#pragma unroll
-      for (int c = 0; c < NT; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  };
   // 8 values of one lane's fragment -> the bf16x8 MFMA operand (fp32: RNE as k_mm_rows rounds)
   auto pack = [&](const float (&v)[8]) __attribute__((always_inline)) {
     bf16x8 r;
@@ -3878,72 +3976,40 @@ k_mm_ring_bf(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ 
     return r;
   };
   const uint32_t bbase = GTA_LDS_ADDR(bres) + static_cast<uint32_t>(lane) * 16u;
-  auto mma_step = [&](const bf16x8 (&a8)[FR], int s) __attribute__((always_inline)) {
-    const uint32_t sb = bbase + static_cast<uint32_t>(s) * 1024u;
-    f32x4 b4[NT];
+  auto stage = [&](int slot, int s) __attribute__((always_inline)) {
+    const uint32_t sa = GTA_LDS_ADDR(lds + slot * STAGE + (wv * FR) * FRAG);
+    f32x4 a4[FR][PA];
 #pragma unroll
-    for (int c = 0; c < NT; ++c) ds_read16_kib(b4[c], sb, c * SB);
+    for (int i = 0; i < FR; ++i)
+#pragma unroll
+      for (int p = 0; p < PA; ++p) ds_read16_kib(a4[i][p], sa + rdoff[p], i * PA);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int c = 0; c < NT; ++c) asm volatile("" : "+v"(b4[c]));
+    for (int i = 0; i < FR; ++i)
 #pragma unroll
-    for (int c = 0; c < NT; ++c) {
-      const bf16x8 b8 = __builtin_bit_cast(bf16x8, b4[c]);
-#pragma unroll
-      for (int i = 0; i < FR; ++i) acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a8[i], b8, acc[i][c], 0, 0, 0);
-    }
-  };
-  const bool vstore = ldo % 4 == 0 && aligned(out, 16);
-  auto epilogue = [&](int64_t j) __attribute__((always_inline)) {
-    const int64_t mw = (grp0 + j * gstep) * GR + wv * (16 * FR);
-    sf_tile(sf, acc);
-    if (vstore) {
-      const int p = r16 & 3, q = r16 >> 2;
+      for (int p = 0; p < PA; ++p) asm volatile("" : "+v"(a4[i][p]));
+    if (ring_tail && s == S - 1) {  // pieces past K: zeros, as k_mm_rows' masked loads give
 #pragma unroll
       for (int i = 0; i < FR; ++i)
 #pragma unroll
-        for (int c = 0; c < NT; ++c) {
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = acc[i][c][r];
-#pragma unroll
-          for (int m2 = 0; m2 < 2; ++m2) {
-            const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2]), 0xB1, 0xF, 0xF, false));
-            const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2 + 1]), 0xB1, 0xF, 0xF, false));
-            if (p & 1) v[2 * m2] = sb; else v[2 * m2 + 1] = sa;
-          }
-#pragma unroll
-          for (int m2 = 0; m2 < 2; ++m2) {
-            const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2]), 0x4E, 0xF, 0xF, false));
-            const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2 + 2]), 0x4E, 0xF, 0xF, false));
-            if (p & 2) v[m2] = sb; else v[m2 + 2] = sa;
-          }
-          const int64_t m = mw + 16 * i + 4 * g + p;
-          const int n = n0 + 16 * c + 4 * q;
-          if (m < M) {
-            if (n + 3 < N) {
-              *reinterpret_cast<float4*>(out + m * ldo + n) = make_float4(v[0], v[1], v[2], v[3]);
-            } else {
-#pragma unroll
-              for (int r = 0; r < 4; ++r)
-                if (n + r < N) out[m * ldo + n + r] = v[r];
-            }
-          }
-        }
-    } else {
-#pragma unroll
-      for (int i = 0; i < FR; ++i)
-#pragma unroll
-        for (int c = 0; c < NT; ++c)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int64_t m = mw + 16 * i + 4 * g + r;
-            const int n = n0 + 16 * c + r16;
-            if (m < M && n < N) out[m * ldo + n] = acc[i][c][r];
-          }
+        for (int p = 0; p < PA; ++p)
+          if (8 * g + 4 * p >= kdead) a4[i][p] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
+    bf16x8 a8[FR];
+#pragma unroll
+    for (int i = 0; i < FR; ++i) {
+      if constexpr (PA == 2) {
+        const float v[8] = {a4[i][0][0], a4[i][0][1], a4[i][0][2], a4[i][0][3],
+                            a4[i][1][0], a4[i][1][1], a4[i][1][2], a4[i][1][3]};
+        a8[i] = pack(v);
+      } else {
+        a8[i] = __builtin_bit_cast(bf16x8, a4[i][0]);
+      }
+    }
+    mma_bf_resident(acc, a8, bbase + static_cast<uint32_t>(s) * 1024u, 0, SB);
   };
   auto tail = [&](int64_t j) __attribute__((always_inline)) {  // k in [32 S, K): masked register step
+    if (ring_tail || K % KS == 0) return;
     const int k0 = S * KS + 8 * g;
     bf16x8 a8[FR];
 #pragma unroll
@@ -3954,59 +4020,15 @@ k_mm_ring_bf(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ 
       for (int q = 0; q < 8; ++q) v[q] = (k0 + q < K) ? load_elem(p + q) : 0.f;
       a8[i] = pack(v);
     }
-    mma_step(a8, S);
+    mma_bf_resident(acc, a8, bbase + static_cast<uint32_t>(S) * 1024u, 0, SB);
   };
-  zero_acc();
+  const bool vstore = ldo % 4 == 0 && aligned(out, 16);
+  auto epilogue = [&](int64_t j) __attribute__((always_inline)) {
+    sf_tile(sf, acc);
+    store_tile(acc, out, ldo, M, N, rs.first_row(j, GR) + wv * (16 * FR), n0, lane, vstore);
+  };
   __syncthreads();  // W^T resident before any fragment read
-#pragma unroll
-  for (int p = 0; p + 1 < D; ++p)
-    if (p < T) issue();
-  int64_t t = 0;
-  int slot = 0;
-  for (int64_t j = 0; j < my_groups; ++j) {
-    for (int s = 0; s < S; ++s, ++t, slot = slot + 1 == D ? 0 : slot + 1) {
-      const int64_t later = T - 1 - t;
-      vm_wait_stages<PER_STAGE>(static_cast<int>(later < D - 2 ? later : D - 2));
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      if (t + D - 1 < T) issue();
-      const uint32_t sa = GTA_LDS_ADDR(lds + slot * STAGE + (wv * FR) * FRAG);
-      f32x4 a4[FR][PA];
-#pragma unroll
-      for (int i = 0; i < FR; ++i)
-#pragma unroll
-        for (int p = 0; p < PA; ++p) ds_read16_idx(a4[i][p], sa + rdoff[p], i * PA);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < FR; ++i)
-#pragma unroll
-        for (int p = 0; p < PA; ++p) asm volatile("" : "+v"(a4[i][p]));
-      if (ring_tail && s == S - 1) {  // pieces past K: zeros, as k_mm_rows' masked loads give
-#pragma unroll
-        for (int i = 0; i < FR; ++i)
-#pragma unroll
-          for (int p = 0; p < PA; ++p)
-            if (8 * g + 4 * p >= kdead) a4[i][p] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      bf16x8 a8[FR];
-#pragma unroll
-      for (int i = 0; i < FR; ++i) {
-        if constexpr (PA == 2) {
-          const float v[8] = {a4[i][0][0], a4[i][0][1], a4[i][0][2], a4[i][0][3],
-                              a4[i][1][0], a4[i][1][1], a4[i][1][2], a4[i][1][3]};
-          a8[i] = pack(v);
-        } else {
-          a8[i] = __builtin_bit_cast(bf16x8, a4[i][0]);
-        }
-      }
-      mma_step(a8, s);
-    }
-    if (!ring_tail && (K % KS)) tail(j);
-    epilogue(j);
-    zero_acc();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  ring_run<PER_STAGE>(rs, acc, issue, stage, tail, epilogue);
 }
 
 // Two chained node GEMMs in one pass (GIN's MLP, `vTCAD/GraphOP/genGraphOP.py:103-108`: applynode
@@ -4041,19 +4063,10 @@ k_mlp_bf(const TA* __restrict__ x, int64_t ldx, int64_t M, int K1, const uint16_
   const int lane = threadIdx.x & (kWave - 1);
   const int wv = wave_id_uniform();
   const int g = lane >> 4, r16 = lane & 15;
-  // W1^T, W2^T resident: fragment (w, c, s) at wres + ((w * NT + c) * SB + s) KiB: lane L's 8 bf16 of
-  // row 16c + (L & 15), k = 32s + 8(L >> 4); zeros past K (W1: K1, W2: N1) and N
-  for (int e = threadIdx.x; e < 2 * NT * SB * kWave; e += kBlock) {
-    const int L = e & (kWave - 1), f = e >> 6, w = f / (NT * SB), c = (f / SB) % NT, st = f % SB;
-    const int n = 16 * c + (L & 15), k = 32 * st + 8 * (L >> 4);
-    const uint16_t* wt = w ? w2t : w1t;
-    const int64_t ldw = w ? ldw2 : ldw1;
-    const int Kw = w ? N1 : K1, Nw = w ? N2 : N1;
-    uint16_t tmp[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) tmp[q] = (n < Nw && k + q < Kw) ? wt[static_cast<int64_t>(n) * ldw + k + q] : 0;
-    *reinterpret_cast<uint4*>(wres + f * 1024 + L * 16) = *reinterpret_cast<const uint4*>(tmp);
-  }
+  // W1^T, W2^T resident: fragment (w, c, s) at wres + ((w * NT + c) * SB + s) KiB; zeros past K (W1:
+  // K1, W2: N1) and N
+  stage_wt_frags<NT, SB>(wres, w1t, ldw1, 0, N1, K1);
+  stage_wt_frags<NT, SB>(wres + NT * SB * 1024, w2t, ldw2, 0, N2, N1);
   __syncthreads();
   const int64_t n_groups = (M + 15) / 16;
   const int64_t gstep = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
@@ -4126,28 +4139,19 @@ k_mlp_bf(const TA* __restrict__ x, int64_t ldx, int64_t M, int K1, const uint16_
   // one 16-row group: GEMM 1, the z image, GEMM 2, the stores
   auto compute = [&](const f32x4 (&xa)[SB][2], int64_t grp) __attribute__((always_inline)) {
     f32x4 acc[1][NT];
-#pragma unroll
-    for (int c = 0; c < NT; ++c) acc[0][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_tile(acc);
     // GEMM 1: k_mm_ring_bf's step order, every step padded with zeros past K1
 #pragma unroll
     for (int st = 0; st < SB; ++st) {
       if (32 * st >= K1) break;  // (wave-uniform)
-      bf16x8 a8;  // x rounded to bf16 (RNE) as k_mm_ring_bf rounds it (a bf16 x: its own bits)
+      bf16x8 a8[1];  // x rounded to bf16 (RNE) as k_mm_ring_bf rounds it (a bf16 x: its own bits)
       if constexpr (XB) {
-        a8 = __builtin_bit_cast(bf16x8, xa[st][0]);
+        a8[0] = __builtin_bit_cast(bf16x8, xa[st][0]);
       } else {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) a8[q] = static_cast<short>(to_bf16_bits(xa[st][q >> 2][q & 3]));
+        for (int q = 0; q < 8; ++q) a8[0][q] = static_cast<short>(to_bf16_bits(xa[st][q >> 2][q & 3]));
       }
-      f32x4 b4[NT];
-#pragma unroll
-      for (int c = 0; c < NT; ++c) ds_read16_kib(b4[c], wbase, c * SB + st);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int c = 0; c < NT; ++c) asm volatile("" : "+v"(b4[c]));
-#pragma unroll
-      for (int c = 0; c < NT; ++c)
-        acc[0][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a8, __builtin_bit_cast(bf16x8, b4[c]), acc[0][c], 0, 0, 0);
+      mma_bf_resident(acc, a8, wbase, st, SB);
     }
     sf_acc(acc, sf1, std::integral_constant<int, SF1>{});
     // z tile -> bf16 image [16 rows][128 k] of this wave: lane (g, 4qq + p) holds rows 4g + r, column
@@ -4158,18 +4162,7 @@ k_mlp_bf(const TA* __restrict__ x, int64_t ldx, int64_t M, int K1, const uint16_
       float v[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = acc[0][c][r];
-#pragma unroll
-      for (int m2 = 0; m2 < 2; ++m2) {
-        const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2]), 0xB1, 0xF, 0xF, false));
-        const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2 + 1]), 0xB1, 0xF, 0xF, false));
-        if (p & 1) v[2 * m2] = sb; else v[2 * m2 + 1] = sa;
-      }
-#pragma unroll
-      for (int m2 = 0; m2 < 2; ++m2) {
-        const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2]), 0x4E, 0xF, 0xF, false));
-        const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2 + 2]), 0x4E, 0xF, 0xF, false));
-        if (p & 2) v[m2] = sb; else v[m2 + 2] = sa;
-      }
+      quad_transpose(v, p);
       const int row = 4 * g + p, col = 16 * c + 4 * qq;  // columns past N1 are zero (K of GEMM 2)
       uint32_t lo = 0, hi = 0;
       if (col < N1) lo |= to_bf16_bits(v[0]);
@@ -4181,66 +4174,15 @@ k_mlp_bf(const TA* __restrict__ x, int64_t ldx, int64_t M, int K1, const uint16_
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     // GEMM 2: A fragment (row r16, k = 32 s + 8 g .. +7) = logical piece 4 s + g of row r16
-#pragma unroll
-    for (int c = 0; c < NT; ++c) acc[0][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_tile(acc);
 #pragma unroll
     for (int st = 0; st < SB; ++st) {
-      f32x4 a4, b4[NT];
-      const uint32_t ra = zw + static_cast<uint32_t>(r16 * 256 + (((4 * st + g) ^ r16) * 16));
-      ds_read16<0>(a4, ra);
-#pragma unroll
-      for (int c = 0; c < NT; ++c) ds_read16_kib(b4[c], wbase, NT * SB + c * SB + st);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      asm volatile("" : "+v"(a4));
-#pragma unroll
-      for (int c = 0; c < NT; ++c) asm volatile("" : "+v"(b4[c]));
-      const bf16x8 a8 = __builtin_bit_cast(bf16x8, a4);
-#pragma unroll
-      for (int c = 0; c < NT; ++c)
-        acc[0][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a8, __builtin_bit_cast(bf16x8, b4[c]), acc[0][c], 0, 0, 0);
+      f32x4 a4[1];  // (lands under mma_bf_resident's wait, which pins it before its first use)
+      ds_read16<0>(a4[0], zw + static_cast<uint32_t>(r16 * 256 + (((4 * st + g) ^ r16) * 16)));
+      mma_bf_resident(acc, a4, wbase, NT * SB + st, SB);
     }
     sf_acc(acc, sf2, std::integral_constant<int, SF2>{});
-    const int64_t mw = grp * 16;
-    if (vstore) {
-#pragma unroll
-      for (int c = 0; c < NT; ++c) {
-        float v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = acc[0][c][r];
-#pragma unroll
-        for (int m2 = 0; m2 < 2; ++m2) {
-          const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2]), 0xB1, 0xF, 0xF, false));
-          const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[2 * m2 + 1]), 0xB1, 0xF, 0xF, false));
-          if (p & 1) v[2 * m2] = sb; else v[2 * m2 + 1] = sa;
-        }
-#pragma unroll
-        for (int m2 = 0; m2 < 2; ++m2) {
-          const float sa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2]), 0x4E, 0xF, 0xF, false));
-          const float sb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[m2 + 2]), 0x4E, 0xF, 0xF, false));
-          if (p & 2) v[m2] = sb; else v[m2 + 2] = sa;
-        }
-        const int64_t m = mw + 4 * g + p;
-        const int n = 16 * c + 4 * qq;
-        if (m < M) {
-          if (n + 3 < N2) {
-            *reinterpret_cast<float4*>(out + m * ldo + n) = make_float4(v[0], v[1], v[2], v[3]);
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (n + r < N2) out[m * ldo + n + r] = v[r];
-          }
-        }
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < NT; ++c)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int64_t m = mw + 4 * g + r;
-          const int n = 16 * c + r16;
-          if (m < M && n < N2) out[m * ldo + n] = acc[0][c][r];
-        }
-    }
+    store_tile(acc, out, ldo, M, N2, grp * 16, 0, lane, vstore);
   };
   // three register buffers, two groups' x loads in flight while one group computes (a group's MFMA
   // work is shorter than an HBM round trip; one group ahead left the waves waiting on their loads)
@@ -4562,7 +4504,6 @@ struct Tuning {
   int esm_lane = 1;        // edge-per-lane edge-softmax when H in {4,8,16} and rows are 16-B aligned
   int mm_ring = 1;         // fp32 UPDATE on k_mm_ring (LDS-DMA ring) instead of k_mm_rows
   int mm_ring_fr = 0;      // k_mm_ring A fragments per wave: 2 = 128-row groups, 1 = 64-row groups, 0 = auto
-  int mm_ring_depth = 0;   // k_mm_ring stages: 0 = auto (by blocks per CU), else 3, 4 or 8
   int mm_prefetch = 1;     // k_mm_rows A prefetch: 1 auto, 2 always, 0 never
   int64_t mm_split = -1;   // UPDATE K slices: -1 auto, 0 = never split, n = n slices
   int mm_wave = 1;         // fp32 UPDATE on k_mm_wave (one wave per block, operands in registers): 0 never, 1 auto, 2 always
@@ -4632,7 +4573,6 @@ const Knob* find_knob(const char* key) {
       {"esm_lane", &Tuning::esm_lane, nullptr},
       {"mm_ring", &Tuning::mm_ring, nullptr},
       {"mm_ring_fr", &Tuning::mm_ring_fr, nullptr},
-      {"mm_ring_depth", &Tuning::mm_ring_depth, nullptr},
       {"mm_prefetch", &Tuning::mm_prefetch, nullptr},
       {"mm_split", nullptr, &Tuning::mm_split},
       {"mm_wave", &Tuning::mm_wave, nullptr},
@@ -5953,15 +5893,42 @@ int gta_softmax_shift(const int64_t* indptr, const int32_t* indices, int64_t n_r
   return GTA_OK;
 }
 
+extern "C++" {  // C++ helpers (WavePlan is returned by value) inside the C ABI block
+namespace {
+// The operands of one UPDATE GEMM as the gta_update_mm* entries receive them (w: W for
+// gta_update_mm, W^T for the _t forms).
+struct MmArgs {
+  const void* x;
+  int64_t ldx;
+  const int32_t* row_idx;
+  int64_t M, K;
+  const void* w;
+  int64_t ldw, N;
+  int dtype, sf;
+  float* out;
+  int64_t ldo;
+};
+
+// The checks of the three gta_update_mm* entries, in their order; sizes_ok / ptrs_ok carry what an
+// entry adds to the size and pointer conditions.  GTA_OK with M == 0: nothing to do, and the
+// pointers are not looked at.
+int check_mm(const char* who, const MmArgs& a, bool sizes_ok = true, bool ptrs_ok = true) {
+  const auto bad = [&](int code, const char* what) { return fail(code, std::string(who) + what); };
+  if (a.M < 0 || a.K <= 0 || a.N <= 0 || !sizes_ok) return bad(GTA_ERR_ARG, ": bad sizes");
+  if (a.M == 0) return GTA_OK;
+  if (!a.x || !a.w || !a.out || !ptrs_ok) return bad(GTA_ERR_ARG, ": bad arguments");
+  if (a.K > INT32_MAX || a.N > INT32_MAX) return bad(GTA_ERR_UNSUPPORTED, ": K/N too large");
+  if (a.dtype != GTA_F32 && a.dtype != GTA_BF16 && a.dtype != GTA_F32_BF16) return bad(GTA_ERR_ARG, ": bad dtype");
+  return GTA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
 int gta_update_mm(const void* x, int64_t ldx, const int32_t* row_idx, int64_t M, int64_t K, const void* w,
                   int64_t ldw, int64_t N, int dtype, int sf, float* out, int64_t ldo, void* stream) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
-  if (M < 0 || K <= 0 || N <= 0) return fail(GTA_ERR_ARG, "update_mm: bad sizes");
-  if (M == 0) return GTA_OK;
-  if (!x || !w || !out) return fail(GTA_ERR_ARG, "update_mm: bad arguments");
-  if (K > INT32_MAX || N > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, "update_mm: K/N too large");
-  if (M == 0) return GTA_OK;
-  if (dtype != GTA_F32 && dtype != GTA_BF16 && dtype != GTA_F32_BF16) return fail(GTA_ERR_ARG, "update_mm: bad dtype");
+  const MmArgs a{x, ldx, row_idx, M, K, w, ldw, N, dtype, sf, out, ldo};
+  if (const int rc = check_mm("update_mm", a); rc != GTA_OK || M == 0) return rc;
   const dim3 grid(static_cast<unsigned>((M + 63) / 64), static_cast<unsigned>((N + 63) / 64));
   if (dtype == GTA_F32) {
     k_mm_f32<<<grid, dim3(kBlock), 0, S(stream)>>>(static_cast<const float*>(x), ldx, row_idx, M,
@@ -5971,21 +5938,17 @@ int gta_update_mm(const void* x, int64_t ldx, const int32_t* row_idx, int64_t M,
     k_mm_bf16<uint16_t><<<grid, dim3(kBlock), 0, S(stream)>>>(static_cast<const uint16_t*>(x), ldx, row_idx, M,
                                                               static_cast<int>(K), static_cast<const uint16_t*>(w),
                                                               ldw, static_cast<int>(N), sf, out, ldo);
-  } else if (dtype == GTA_F32_BF16) {
+  } else {
     k_mm_bf16<float><<<grid, dim3(kBlock), 0, S(stream)>>>(static_cast<const float*>(x), ldx, row_idx, M,
                                                            static_cast<int>(K), static_cast<const uint16_t*>(w), ldw,
                                                            static_cast<int>(N), sf, out, ldo);
-  } else {
-    return fail(GTA_ERR_ARG, "update_mm: bad dtype");
   }
   GTA_LAUNCHED("k_mm");
   return GTA_OK;
 }
 
-extern "C++" {  // C++ helpers (WavePlan is returned by value) inside the C ABI block
+extern "C++" {
 namespace {
-// k_mm_ring launch: NT (4: N <= 64, 8: wider), ring depth D (3 / 4 / 8: blocks per CU the grid
-// needs), FR (A fragments per wave); kslice > 0: the split-K form (grid.y = K slices)
 // waves per SIMD k_mm_wave<NT, FR> is built for (its __launch_bounds__): what its registers allow
 constexpr int wave_wps(int NT, int FR) { return NT == 4 || FR <= 2 ? 2 : 1; }
 
@@ -6085,18 +6048,56 @@ bool launch_wave(int nt, hipStream_t s, const float* x, int64_t ldx, int64_t M, 
   return true;
 }
 
-void launch_ring(int nt, int D, int fr, dim3 gr, hipStream_t s, const float* x, int64_t ldx, const int32_t* row_idx,
-                 int64_t M, int K, const float* wt, int64_t ldwt, int N, int sf, float* out, int64_t ldo, int kslice,
-                 int64_t slice_stride) {
-#define GTA_RING(NT_, D_, FR_)                                                                              \
-  k_mm_ring<NT_, D_, FR_><<<gr, dim3(kBlock), 0, s>>>(x, ldx, row_idx, M, K, wt, ldwt, N, sf, out, ldo, kslice, \
-                                                      slice_stride)
+// k_mm_ring launch: NT (4: N <= 64, 8: wider), ring depth D (3: the persistent form, 4: split K),
+// FR (A fragments per wave); kslice > 0: the split-K form (grid.y = K slices)
+void launch_ring(int nt, int D, int fr, dim3 gr, hipStream_t s, const MmArgs& a, int kslice, int64_t slice_stride) {
+#define GTA_RING(NT_, D_, FR_)                                                                                      \
+  k_mm_ring<NT_, D_, FR_><<<gr, dim3(kBlock), 0, s>>>(static_cast<const float*>(a.x), a.ldx, a.row_idx, a.M,           \
+                                                      static_cast<int>(a.K), static_cast<const float*>(a.w), a.ldw, \
+                                                      static_cast<int>(a.N), a.sf, a.out, a.ldo, kslice, slice_stride)
 #define GTA_RING_D(NT_, FR_) \
-  if (D == 8) GTA_RING(NT_, 8, FR_); else if (D == 4) GTA_RING(NT_, 4, FR_); else GTA_RING(NT_, 3, FR_)
+  if (D == 4) GTA_RING(NT_, 4, FR_); else GTA_RING(NT_, 3, FR_)
   if (nt == 8) { if (fr == 1) { GTA_RING_D(8, 1); } else { GTA_RING_D(8, 2); } }
   else { if (fr == 1) { GTA_RING_D(4, 1); } else { GTA_RING_D(4, 2); } }
 #undef GTA_RING_D
 #undef GTA_RING
+}
+
+// k_mm_rows launch: the TA / WT / NT / PF ladder (pf: prefetch the next A fragment); kslice > 0:
+// the split-K form (grid.y = K slices, slice y into a.out + y * oslice)
+void launch_rows(int dtype, int nt, bool pf, dim3 gr, hipStream_t s, const MmArgs& a, int64_t kslice, int64_t oslice) {
+#define GTA_MMR(TA_, WT_, NT_, PF_)                                                                             \
+  k_mm_rows<TA_, WT_, NT_, PF_><<<gr, dim3(kBlock), 0, s>>>(static_cast<const TA_*>(a.x), a.ldx, a.row_idx, a.M,     \
+                                                            static_cast<int>(a.K), static_cast<const WT_*>(a.w),   \
+                                                            a.ldw, static_cast<int>(a.N), a.sf, a.out, a.ldo,      \
+                                                            kslice, oslice, 1)
+#define GTA_MMR_PF(TA_, WT_, NT_) \
+  if (pf) GTA_MMR(TA_, WT_, NT_, true); else GTA_MMR(TA_, WT_, NT_, false)
+#define GTA_MMR_NT(TA_, WT_)                                                                            \
+  if (nt == 1) { GTA_MMR_PF(TA_, WT_, 1); } else if (nt == 2) { GTA_MMR_PF(TA_, WT_, 2); }              \
+  else if (nt == 4) { GTA_MMR_PF(TA_, WT_, 4); } else { GTA_MMR_PF(TA_, WT_, 8); }
+  if (dtype == GTA_F32) { GTA_MMR_NT(float, float) }
+  else if (dtype == GTA_BF16) { GTA_MMR_NT(uint16_t, uint16_t) }
+  else { GTA_MMR_NT(float, uint16_t) }
+#undef GTA_MMR_NT
+#undef GTA_MMR_PF
+#undef GTA_MMR
+}
+
+// CUs the persistent grids are sized for (an MI355X)
+constexpr int64_t kMmCUs = 256;
+
+// a persistent grid: per_cu blocks on every CU, whole column-block sets, at most one block per row group
+inline int64_t persistent_blocks(int64_t n_grp, int64_t ncb, int64_t per_cu) {
+  return std::min(n_grp, std::max<int64_t>(1, kMmCUs * per_cu / ncb)) * ncb;
+}
+
+// k_mm_rows prefetches the next A fragment: measured 1.2x on fp32 (K = 602) and bf16 K = 128, and 1.1x
+// on the mixed path with a K tail since fp32 A loads are float4 pieces (GIN K = 100: 0.70 -> 0.64 ms,
+// profiles/r01_mm_bench_2.json); bf16 x with a K tail (k: K, or the K slice) stays without;
+// tuning().mm_prefetch 2 = always, 0 = never
+inline bool rows_prefetch(int dtype, int64_t k) {
+  return tuning().mm_prefetch == 2 || (tuning().mm_prefetch == 1 && (dtype != GTA_BF16 || k % 32 == 0));
 }
 
 inline int mm_nt(int64_t N) { return N <= 16 ? 1 : N <= 32 ? 2 : N <= 64 ? 4 : 8; }
@@ -6125,24 +6126,20 @@ int64_t gta_update_mm_t_splits(int64_t M, int64_t K, int64_t N, int dtype, void*
   if (K < 256 || units >= 128) return 1;
   // the ring (fp32): one (group, slice) block per CU, every block resident at once; k_mm_rows
   // (bf16 / mixed, several blocks per CU): about two per CU; slices of >= 64 k
-  const int64_t want = (dtype == GTA_F32 ? 256 : 512) / std::max<int64_t>(1, units);
+  const int64_t want = (dtype == GTA_F32 ? kMmCUs : 2 * kMmCUs) / std::max<int64_t>(1, units);
   return std::max<int64_t>(1, std::min<int64_t>({want, K / 64, dtype == GTA_F32 ? 32 : 16}));
 }
 
 int gta_update_mm_t(const void* x, int64_t ldx, const int32_t* row_idx, int64_t M, int64_t K, const void* wt,
                     int64_t ldwt, int64_t N, int dtype, int sf, float* out, int64_t ldo, void* stream) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
-  if (M < 0 || K <= 0 || N <= 0 || ldwt < K) return fail(GTA_ERR_ARG, "update_mm_t: bad sizes");
-  if (M == 0) return GTA_OK;
-  if (!x || !wt || !out) return fail(GTA_ERR_ARG, "update_mm_t: bad arguments");
-  if (K > INT32_MAX || N > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, "update_mm_t: K/N too large");
-  if (dtype != GTA_F32 && dtype != GTA_BF16 && dtype != GTA_F32_BF16) return fail(GTA_ERR_ARG, "update_mm_t: bad dtype");
+  const MmArgs a{x, ldx, row_idx, M, K, wt, ldwt, N, dtype, sf, out, ldo};
+  if (const int rc = check_mm("update_mm_t", a, ldwt >= K); rc != GTA_OK || M == 0) return rc;
   const int nt = mm_nt(N);
   const int64_t groups = (M + 127) / 128;
   const int64_t ncb = (N + 16 * nt - 1) / (16 * nt);
-  // (mm_ring = 0 selects k_mm_rows, and a forced ring shape (mm_ring_fr / mm_ring_depth) the ring)
-  if (dtype == GTA_F32 && tuning().mm_wave && tuning().mm_ring && !tuning().mm_ring_fr && !tuning().mm_ring_depth &&
-      !row_idx && K >= 16 &&
+  // (mm_ring = 0 selects k_mm_rows, and a forced ring shape (mm_ring_fr) the ring)
+  if (dtype == GTA_F32 && tuning().mm_wave && tuning().mm_ring && !tuning().mm_ring_fr && !row_idx && K >= 16 &&
       launch_wave(nt, S(stream), static_cast<const float*>(x), ldx, M, static_cast<int>(K), static_cast<const float*>(wt),
                   ldwt, static_cast<int>(N), sf, out, ldo)) {
     GTA_LAUNCHED("k_mm_wave");
@@ -6154,24 +6151,15 @@ int gta_update_mm_t(const void* x, int64_t ldx, const int32_t* row_idx, int64_t 
     // most, or when there are too few 128-row groups for two blocks per CU (K = 128 / 256 at 232,965
     // rows 77 -> 86 / 92 -> 96 TF/s, 16,384 rows 40 -> 69; profiles/r02_mm_ring_probe_fr.json)
     const int frk = tuning().mm_ring_fr;
-    const double per_cu2 = static_cast<double>(groups * ncb) / 256.0;
+    const double per_cu2 = static_cast<double>(groups * ncb) / static_cast<double>(kMmCUs);
     const bool uneven = per_cu2 / std::ceil(per_cu2) < 0.95;
     const int fr = (frk == 1 || (frk == 0 && ((K <= 256 && uneven) || groups < 512))) ? 1 : 2;
     const int64_t n_grp = fr == 1 ? (M + 63) / 64 : groups;
     // the persistent 3-deep ring with every CU slot its LDS allows filled (each CU the same number of
     // row groups +-1; profiles/r02_mm_ring_probe.json); 4 or 8 stages at fewer blocks per CU were
-    // measured slower on every shape from 16,384 to 232,965 rows (profiles/r03_mm_depth_sweep.log)
-    int D = 3;
-    const int64_t per_cu3 = nt == 8 ? (fr == 1 ? 4 : 3) : 4;  // ring_blocks(NT, 3, FR)
-    int64_t blocks = std::min(n_grp, std::max<int64_t>(1, 256 * per_cu3 / ncb)) * ncb;
-    const int dk = tuning().mm_ring_depth;
-    if (dk == 3 || dk == 4 || dk == 8) {  // forced depth: a persistent grid of what that ring's LDS allows
-      const int64_t per_cu = dk == 8 ? 1 : dk == 4 ? (nt == 8 && fr == 2 ? 2 : 3) : (nt == 8 ? (fr == 1 ? 4 : 3) : 4);
-      D = dk;
-      blocks = std::min(n_grp, std::max<int64_t>(1, 256 * per_cu / ncb)) * ncb;
-    }
-    launch_ring(nt, D, fr, dim3(static_cast<unsigned>(blocks)), S(stream), static_cast<const float*>(x), ldx, row_idx, M,
-                static_cast<int>(K), static_cast<const float*>(wt), ldwt, static_cast<int>(N), sf, out, ldo, 0, 0);
+    // measured slower on every shape from 16,384 to 232,965 rows (profiles/r03/mm_depth_sweep.log)
+    const int64_t blocks = persistent_blocks(n_grp, ncb, ring_blocks(nt, 3, fr));
+    launch_ring(nt, 3, fr, dim3(static_cast<unsigned>(blocks)), S(stream), a, 0, 0);
     GTA_LAUNCHED("k_mm_ring");
     return GTA_OK;
   }
@@ -6182,9 +6170,7 @@ int gta_update_mm_t(const void* x, int64_t ldx, const int32_t* row_idx, int64_t 
     const int fr = tuning().mm_ring_fr == 2 ? 2 : 1;
     const int sb = K <= 128 ? 4 : 8;
     const int64_t n_grp = fr == 1 ? (M + 63) / 64 : groups;
-    const int64_t per_cu = 2;
-    const int64_t blocks = std::min(n_grp, std::max<int64_t>(1, 256 * per_cu / ncb)) * ncb;
-    const dim3 gr(static_cast<unsigned>(blocks));
+    const dim3 gr(static_cast<unsigned>(persistent_blocks(n_grp, ncb, 2)));
 #define GTA_RBF(TA_, NT_, D_, FR_, SB_)                                                                        \
   k_mm_ring_bf<TA_, NT_, D_, FR_, SB_><<<gr, dim3(kBlock), 0, S(stream)>>>(static_cast<const TA_*>(x), ldx, row_idx, M, \
                                                                           static_cast<int>(K),                       \
@@ -6201,28 +6187,9 @@ int gta_update_mm_t(const void* x, int64_t ldx, const int32_t* row_idx, int64_t 
     GTA_LAUNCHED("k_mm_ring_bf");
     return GTA_OK;
   }
-  const int64_t per_cu = 8;
   const int kc = (dtype == GTA_F32) ? (nt >= 8 ? 64 : 128) : (nt >= 8 ? 128 : 256);  // k_mm_rows KC
-  const int64_t cap = (K <= kc) ? std::max<int64_t>(1, 256 * per_cu / ncb) : groups;  // W staged once: persistent
-  const dim3 gr(static_cast<unsigned>(std::min<int64_t>(groups, cap) * ncb));
-  // prefetch the next A fragment: measured 1.2x on fp32 (K = 602) and bf16 K = 128, and 1.1x on the
-  // mixed path with a K tail since fp32 A loads are float4 pieces (GIN K = 100: 0.70 -> 0.64 ms,
-  // profiles/r01_mm_bench_2.json); bf16 x with a K tail stays without; tuning().mm_prefetch 2 = always, 0 = never
-  const bool pf = tuning().mm_prefetch == 2 || (tuning().mm_prefetch == 1 && (dtype != GTA_BF16 || K % 32 == 0));
-#define GTA_MMR(TA_, WT_, NT_)                                                                                \
-  if (pf) k_mm_rows<TA_, WT_, NT_, true><<<gr, dim3(kBlock), 0, S(stream)>>>(                        \
-      static_cast<const TA_*>(x), ldx, row_idx, M, static_cast<int>(K), static_cast<const WT_*>(wt), ldwt,        \
-      static_cast<int>(N), sf, out, ldo, 0, 0, 1);                                                      \
-  else k_mm_rows<TA_, WT_, NT_><<<gr, dim3(kBlock), 0, S(stream)>>>(static_cast<const TA_*>(x), ldx, row_idx, M, \
-                                                                    static_cast<int>(K), static_cast<const WT_*>(wt), \
-                                                                    ldwt, static_cast<int>(N), sf, out, ldo, 0, 0, 1)
-#define GTA_MMR_NT(TA_, WT_) \
-  if (nt == 1) GTA_MMR(TA_, WT_, 1); else if (nt == 2) GTA_MMR(TA_, WT_, 2); else if (nt == 4) GTA_MMR(TA_, WT_, 4); else GTA_MMR(TA_, WT_, 8)
-  if (dtype == GTA_F32) { GTA_MMR_NT(float, float); }
-  else if (dtype == GTA_BF16) { GTA_MMR_NT(uint16_t, uint16_t); }
-  else { GTA_MMR_NT(float, uint16_t); }
-#undef GTA_MMR_NT
-#undef GTA_MMR
+  const int64_t blocks = K <= kc ? persistent_blocks(groups, ncb, 8) : groups * ncb;  // W staged once: persistent
+  launch_rows(dtype, nt, rows_prefetch(dtype, K), dim3(static_cast<unsigned>(blocks)), S(stream), a, 0, 0);
   GTA_LAUNCHED("k_mm_rows");
   return GTA_OK;
 }
@@ -6276,11 +6243,10 @@ int gta_update_mm_t_split(const void* x, int64_t ldx, const int32_t* row_idx, in
                           int64_t ldwt, int64_t N, int dtype, int sf, float* out, int64_t ldo, int64_t splits,
                           void* workspace, int64_t workspace_bytes, void* stream) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
-  if (M < 0 || K <= 0 || N <= 0 || ldwt < K || splits < 1) return fail(GTA_ERR_ARG, "update_mm_t_split: bad sizes");
-  if (M == 0) return GTA_OK;
-  if (!x || !wt || !out || !workspace) return fail(GTA_ERR_ARG, "update_mm_t_split: bad arguments");
-  if (K > INT32_MAX || N > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, "update_mm_t_split: K/N too large");
-  if (dtype != GTA_F32 && dtype != GTA_BF16 && dtype != GTA_F32_BF16) return fail(GTA_ERR_ARG, "update_mm_t_split: bad dtype");
+  const MmArgs a{x, ldx, row_idx, M, K, wt, ldwt, N, dtype, sf, out, ldo};
+  if (const int rc = check_mm("update_mm_t_split", a, ldwt >= K && splits >= 1, workspace != nullptr);
+      rc != GTA_OK || M == 0)
+    return rc;
   if (workspace_bytes < splits * M * N * static_cast<int64_t>(sizeof(float)))
     return fail(GTA_ERR_ARG, "update_mm_t_split: workspace too small");
   float* ws = static_cast<float*>(workspace);
@@ -6291,35 +6257,24 @@ int gta_update_mm_t_split(const void* x, int64_t ldx, const int32_t* row_idx, in
   const bool ring = ring_ok(dtype, nt, x, wt, ldwt) && N % 4 == 0 && aligned(ws, 16);
   const int64_t ks = mm_kslice(K, splits), nsl = (K + ks - 1) / ks;
   if (nsl > 65535) return fail(GTA_ERR_UNSUPPORTED, "update_mm_t_split: too many slices");
+  MmArgs part = a;  // the slices: dense [M, N] partial sums in the workspace, no SF
+  part.out = ws;
+  part.ldo = N;
   if (ring) {
     // every (64-row group, K slice) on its own block, a 4-deep ring at three blocks per CU, then the
     // ordered slice sum.  GCN Cora's [2708 x 1433].[1433 x 128]: 43 groups x 10 slices of 144 k,
     // 28.8 us against 31.5 for 128-row groups on an 8-deep ring at one block per CU
-    // (profiles/r03/mm_cora_epilogue.log); mm_ring_fr = 2 / mm_ring_depth = 3 or 8 select those
-    const int dk = tuning().mm_ring_depth;
+    // (profiles/r03/mm_cora_epilogue.log); mm_ring_fr = 2 selects 128-row groups
     const int fr = tuning().mm_ring_fr == 2 ? 2 : 1;
     const int64_t n_grp = fr == 1 ? (M + 63) / 64 : groups;
-    launch_ring(nt, dk == 3 || dk == 8 ? dk : 4, fr, dim3(static_cast<unsigned>(n_grp * ncb), static_cast<unsigned>(nsl)), s,
-                static_cast<const float*>(x), ldx, row_idx, M, static_cast<int>(K), static_cast<const float*>(wt), ldwt,
-                static_cast<int>(N), GTA_SF_NONE, ws, N, static_cast<int>(ks), M * N);
+    part.sf = GTA_SF_NONE;
+    launch_ring(nt, 4, fr, dim3(static_cast<unsigned>(n_grp * ncb), static_cast<unsigned>(nsl)), s, part,
+                static_cast<int>(ks), M * N);
     GTA_LAUNCHED("k_mm_ring<split>");
   } else {
-  const dim3 gr(static_cast<unsigned>(groups * ncb), static_cast<unsigned>(nsl));
-  const bool pf = tuning().mm_prefetch == 2 || (tuning().mm_prefetch == 1 && (dtype != GTA_BF16 || ks % 32 == 0));
-  const int ki = static_cast<int>(K);
-#define GTA_MMS(TA_, WT_, NT_)                                                                                    \
-  if (pf) k_mm_rows<TA_, WT_, NT_, true><<<gr, dim3(kBlock), 0, s>>>(static_cast<const TA_*>(x), ldx, row_idx, M, ki, \
-      static_cast<const WT_*>(wt), ldwt, static_cast<int>(N), sf, ws, N, ks, M * N, 1);                                 \
-  else k_mm_rows<TA_, WT_, NT_><<<gr, dim3(kBlock), 0, s>>>(static_cast<const TA_*>(x), ldx, row_idx, M, ki,          \
-      static_cast<const WT_*>(wt), ldwt, static_cast<int>(N), sf, ws, N, ks, M * N, 1)
-#define GTA_MMS_NT(TA_, WT_) \
-  if (nt == 1) GTA_MMS(TA_, WT_, 1); else if (nt == 2) GTA_MMS(TA_, WT_, 2); else if (nt == 4) GTA_MMS(TA_, WT_, 4); else GTA_MMS(TA_, WT_, 8)
-  if (dtype == GTA_F32) { GTA_MMS_NT(float, float); }
-  else if (dtype == GTA_BF16) { GTA_MMS_NT(uint16_t, uint16_t); }
-  else { GTA_MMS_NT(float, uint16_t); }
-#undef GTA_MMS_NT
-#undef GTA_MMS
-  GTA_LAUNCHED("k_mm_rows<split>");
+    launch_rows(dtype, nt, rows_prefetch(dtype, ks), dim3(static_cast<unsigned>(groups * ncb), static_cast<unsigned>(nsl)),
+                s, part, ks, M * N);
+    GTA_LAUNCHED("k_mm_rows<split>");
   }
   const int64_t total = M * N;
   if (N % 4 == 0 && ldo % 4 == 0 && aligned(out, 16) && aligned(ws, 16)) {

@@ -1244,7 +1244,8 @@ def test_update_mlp_bf16_x(dev, M, K1, N1, N2, sf1, sf2):
 
 @pytest.mark.parametrize("M,K1,N1,N2,sf1,sf2", [(20000, 100, 128, 128, "RELU", "RELU"), (4099, 128, 128, 128, None, "ELU"),
                                                 (3001, 64, 96, 48, "SIGMOID", None), (777, 100, 128, 100, "RELU", None),
-                                                (33, 36, 20, 8, "EXP", "RELU"), (5, 128, 128, 128, "RELU", "RELU")])
+                                                (33, 36, 20, 8, "EXP", "RELU"), (5, 128, 128, 128, "RELU", "RELU"),
+                                                (100003, 100, 128, 128, "RELU", None)])
 def test_update_mlp_bitwise(dev, M, K1, N1, N2, sf1, sf2):
     """gta_update_mlp (GIN's MM -> SF -> MM -> SF in one pass, no [M, N1] intermediate in HBM) ==
     the two unfused mixed-precision UPDATEs bitwise: fp32 x rounded to bf16 as the first GEMM stages
