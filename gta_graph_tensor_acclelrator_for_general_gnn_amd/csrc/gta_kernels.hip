@@ -1040,6 +1040,9 @@ template <> struct Row4<true> {
   typedef uint2 type;
   static __device__ __forceinline__ uint2 zero() { return make_uint2(0u, 0u); }
 };
+// keeps a row piece's registers written where the source writes them (no code)
+__device__ __forceinline__ void row4_pin(float4& r) { asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w)); }
+__device__ __forceinline__ void row4_pin(uint2& r) { asm volatile("" : "+v"(r.x), "+v"(r.y)); }
 __device__ __forceinline__ float4 row4_f32(const float4& r) { return r; }
 __device__ __forceinline__ float4 row4_f32(const uint2& r) {
   return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
@@ -1388,13 +1391,136 @@ __device__ __forceinline__ void h32_walk(const int32_t* indices, const int64_t* 
   if (len > 0) slab_store<(NT & 2) != 0>(slabs + d.k * F + l32 * 4, acc);
 }
 
-template <bool WEIGHTED, int NT, bool W1 = false, bool A1 = false, bool BF = false>
+// A1: a step's weights from the lane's one 8-B load pr (odd: the lane's head is odd) -- wu[u] is
+// edge u's weight of the lane's head
+__device__ __forceinline__ void a1_spread(const float2 pr, const bool odd, float (&wu)[8]) {
+  const float own = odd ? pr.y : pr.x, oth = xmask4(odd ? pr.x : pr.y, odd);
+  float a[4], b[4];
+  a[0] = quad_bcast<0>(own); b[0] = quad_bcast<0>(oth);
+  a[1] = quad_bcast<1>(own); b[1] = quad_bcast<1>(oth);
+  a[2] = quad_bcast<2>(own); b[2] = quad_bcast<2>(oth);
+  a[3] = quad_bcast<3>(own); b[3] = quad_bcast<3>(oth);
+#pragma unroll
+  for (int k2 = 0; k2 < 4; ++k2) {
+    wu[2 * k2] = odd ? b[k2] : a[k2];
+    wu[2 * k2 + 1] = odd ? a[k2] : b[k2];
+  }
+}
+
+// GR (A1 with ldw == 8, weights and indices 128-B aligned; knob seg_grid): the A1 walk with its
+// steps on the global edge grid instead of at the item's first edge.  An item [beg, beg + len)
+// walks the aligned 8-edge windows from beg & ~7, so a step's 8 x 8 weights are exactly two 128-B
+// lines (2.75 on average from an arbitrary beg) and the first and last steps mask the edges
+// outside the item: those lanes load no weight (w = +0 through the DPP spread) and gather no row
+// (x = 0), as the tail steps of the walk above.  The indices come by aligned 32-edge chunks, one
+// line per load: lane l holds entry (l + r) & 31 of its chunk, r = beg & 24, so lanes l < 32 - r
+// of chunk m and l >= 32 - r of chunk m + 1 together are the 32 edges from (beg & ~7) + 32 m in
+// lane order -- one select per 32 edges, then the walk's fixed broadcasts.  Items are clamped to
+// nnz: no index or weight outside [0, nnz) is read.  Same per-lane edge order and fma chain as
+// the A1 form: bitwise equal to it.
+template <int NT, bool BF>
+__device__ __forceinline__ void h32_grid_walk(const int32_t* indices, const int64_t* n_items_p,
+                                              const float* x, uint32_t row_bytes, const float* w,
+                                              uint32_t nnz, float* slabs, const SegItem* items) {
+  constexpr int G = 32, F = 128, U = 8;
+  typedef typename Row4<BF>::type XR;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int l32 = lane & (G - 1);
+  const ItemSlot d = item_decode<G>(n_items_p, items, lane);
+  const uint32_t beg = static_cast<uint32_t>(d.it.beg);  // host: nnz * 32 < 2^32
+  const uint32_t last = min(beg + static_cast<uint32_t>(max(d.it.len, 0)), nnz);
+  const uint32_t len = last > beg ? last - beg : 0u;
+  const uint32_t end = len ? last : 0u;  // an empty item loads nothing
+  const int f = len ? static_cast<int>(beg & 7u) : 0;  // edges of the first window before the item
+  const int glen = len ? f + static_cast<int>(len) : 0;  // the item's end, counted from beg & ~7
+  const int other = __shfl_xor(glen, 32);
+  const int gmax = __builtin_amdgcn_readfirstlane(max(glen, other));
+  const int gmin = __builtin_amdgcn_readfirstlane(min(glen, other));
+  if (gmax == 0) return;
+  const bool front = __ballot(f != 0) != 0;  // some item of the wave starts inside its first window
+  const uint32_t colb = static_cast<uint32_t>(l32) * (BF ? 8u : 16u);
+  const char* xb = reinterpret_cast<const char*>(x);
+  const int h = l32 >> 2, q = l32 & 3;
+  const bool odd = h & 1;
+  const int wl = 2 * q + (h & 1);  // the window's edge whose weights this lane loads (heads h & ~1, h | 1)
+  const char* wbase = reinterpret_cast<const char*>(w);
+  uint32_t woff = (((beg & ~7u) + static_cast<uint32_t>(wl)) * 8u + static_cast<uint32_t>(h & ~1)) * 4u;
+  const char* ibase = reinterpret_cast<const char*>(indices);
+  const uint32_t r = beg & 24u;
+  const bool lo = static_cast<uint32_t>(l32) + r < 32u;
+  uint32_t ie = (beg & ~31u) + ((static_cast<uint32_t>(l32) + r) & 31u);  // the lane's entry of the chunk
+  auto ldc = [&](uint32_t e) {  // a chunk's entry, where the item needs it
+    if (e >= end) return 0;
+    const int32_t* p = reinterpret_cast<const int32_t*>(ibase + (e << 2));
+    return (NT & 1) ? __builtin_nontemporal_load(p) : *p;
+  };
+  auto wld = [&](uint32_t off) { return *reinterpret_cast<const float2*>(wbase + off); };
+  auto row = [&](int src) { return lean_at<XR>(xb, src, row_bytes, colb); };
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  const int i0 = ldc(ie);
+  int in = ldc(ie + G);
+  int idxv = lo ? i0 : in;  // the 32 edges from beg & ~7, lane = edge
+  ie += 2 * G;
+  for (int c = 0; c < gmax; c += G) {
+    const int inn = ldc(ie);  // two chunks ahead: the next 32 edges end in it
+#pragma unroll
+    for (int s = 0; s < G; s += U) {
+      if (c + s >= gmax) break;
+      XR xv[U];
+      float wu[U];
+      if (c + s + U <= gmin && (s > 0 || c > 0 || !front)) {  // inside both items: no masks
+#pragma unroll
+        for (int u = 0; u < U; ++u) xv[u] = row(bcastG<G>(idxv, s + u));
+        a1_spread(wld(woff + static_cast<uint32_t>(s) * 32u), odd, wu);
+      } else {
+        const int p = c + s - f;  // the window's first edge, counted from beg (may be < 0)
+        // the masked rows' zeros are written here, before any load of the step is issued: written
+        // edge by edge between the gathers, each write waited for the loads issued before it
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          xv[u] = Row4<BF>::zero();
+          row4_pin(xv[u]);
+        }
+        float2 pr = make_float2(0.f, 0.f);
+        if (static_cast<uint32_t>(p + wl) < len) pr = wld(woff + static_cast<uint32_t>(s) * 32u);
+        int src[U];  // the eight broadcasts back to back, ahead of the masked gathers
+#pragma unroll
+        for (int u = 0; u < U; ++u) src[u] = bcastG<G>(idxv, s + u);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (static_cast<uint32_t>(p + u) < len) xv[u] = row(src[u]);
+        }
+        a1_spread(pr, odd, wu);  // after the gathers are issued; an edge outside the item: no lane loaded it, w = +0
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float4 xw = row4_f32(xv[u]);
+        acc[0] = fmaf(wu[u], xw.x, acc[0]);
+        acc[1] = fmaf(wu[u], xw.y, acc[1]);
+        acc[2] = fmaf(wu[u], xw.z, acc[2]);
+        acc[3] = fmaf(wu[u], xw.w, acc[3]);
+      }
+    }
+    idxv = lo ? in : inn;
+    in = inn;
+    ie += G;
+    woff += static_cast<uint32_t>(G) * 32u;
+  }
+  if (len) slab_store<(NT & 2) != 0>(slabs + d.k * F + l32 * 4, acc);
+}
+
+template <bool WEIGHTED, int NT, bool W1 = false, bool A1 = false, bool BF = false, bool GR = false>
 __global__ void __launch_bounds__(kBlock)
 k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
           uint32_t row_bytes, const float* __restrict__ w, int64_t ldw, float* __restrict__ slabs,
-          const SegItem* __restrict__ items) {
+          const SegItem* __restrict__ items, uint32_t nnz = 0) {
   if constexpr (!WEIGHTED) {  // the plain sum: the shared walk
     h32_walk<NT, BF>(indices, n_items_p, x, row_bytes, slabs, items, FoldSum<BF>{});
+    return;
+  }
+  if constexpr (GR) {  // the A1 walk on the edge grid
+    static_assert(WEIGHTED && A1 && !W1, "the grid walk is a form of A1");
+    h32_grid_walk<NT, BF>(indices, n_items_p, x, row_bytes, w, nnz, slabs, items);
     return;
   }
   constexpr int G = 32, F = 128, U = 8;
@@ -1445,18 +1571,7 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
         } else if (A1) {
           const float2 pr = *reinterpret_cast<const float2*>(
               wbase + (woff + static_cast<uint32_t>((h & 1) + s + 2 * q) * wrow + static_cast<uint32_t>(2 * (h >> 1) - h) * 4u));
-          const bool odd = h & 1;
-          const float own = odd ? pr.y : pr.x, oth = xmask4(odd ? pr.x : pr.y, odd);
-          float a[4], b[4];
-          a[0] = quad_bcast<0>(own); b[0] = quad_bcast<0>(oth);
-          a[1] = quad_bcast<1>(own); b[1] = quad_bcast<1>(oth);
-          a[2] = quad_bcast<2>(own); b[2] = quad_bcast<2>(oth);
-          a[3] = quad_bcast<3>(own); b[3] = quad_bcast<3>(oth);
-#pragma unroll
-          for (int k2 = 0; k2 < 4; ++k2) {
-            wu[2 * k2] = odd ? b[k2] : a[k2];
-            wu[2 * k2 + 1] = odd ? a[k2] : b[k2];
-          }
+          a1_spread(pr, h & 1, wu);
         } else {
           const float* wp = wc + (s + 2 * q) * ldw32;
           const float w0 = ldw_(wp), w1 = ldw_(wp + ldw32);
@@ -4484,6 +4599,8 @@ struct Tuning {
                            // 1 step ahead; 2: 128 B, 1 step; 3: 64 B, 2 steps; 4: 128 B, 2 steps; 5: as 1, held to
                            // 8 waves per SIMD; 0: off)
   int seg_alpha1 = 1;      // k_agg_h32 with 8 heads: one 8-B weight load per lane and step (A1) instead of two 4-B
+  int seg_grid = 1;        // the A1 form with its steps on the aligned 8-edge grid (ldw == 8, w and indices 128-B
+                           // aligned): every weight load two whole lines, every index load one
   int agg_bf16_vw8 = 4;    // k_aggregate over bf16 rows in 16-B pieces (VW = 8) instead of 8-B pieces:
                            // 0 off, 4 / 8 = row loads in flight per lane and step (1 = 4)
   int agg_w1 = 1;          // k_aggregate with one weight per edge: 64 per load, broadcast (WM_EDGE1); 0 = WM_HEAD
@@ -4556,6 +4673,7 @@ const Knob* find_knob(const char* key) {
       {"seg_lean", &Tuning::seg_lean, nullptr},
       {"seg_lean_w1", &Tuning::seg_lean_w1, nullptr},
       {"seg_alpha1", &Tuning::seg_alpha1, nullptr},
+      {"seg_grid", &Tuning::seg_grid, nullptr},
       {"seg_pf", &Tuning::seg_pf, nullptr},
       {"agg_bf16_vw8", &Tuning::agg_bf16_vw8, nullptr},
       {"agg_w1", &Tuning::agg_w1, nullptr},
@@ -5195,6 +5313,8 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
     if (lean) {
       const bool a1 = w && heads == 8 && ldw % 2 == 0 && aligned(w, 8) && tuning().seg_alpha1 &&
                       static_cast<uint64_t>(nnz) * static_cast<uint64_t>(ldw) * 4u < (1ull << 32);
+      // the A1 walk on the edge grid: its aligned windows are whole 128-B lines of w and indices
+      const bool grid = a1 && ldw == 8 && aligned(w, 128) && aligned(indices, 128) && tuning().seg_grid;
       const int pf = tuning().seg_pf;
       const uint32_t wbytes = static_cast<uint32_t>(nnz * ldw * 4), ibytes = static_cast<uint32_t>(nnz * 4);
       auto h32 = [&](auto W, auto NT, auto W1, auto A1) {  // k_agg_h32<WEIGHTED, NT, W1, A1, BF>
@@ -5211,6 +5331,11 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
         if (pf == 1) GTA_PF(64, 0); else if (pf == 2) GTA_PF(128, 0); else if (pf == 3) GTA_PF(64, 1); else if (pf == 4) GTA_PF(128, 1);
         else k_agg_h32pf<3, 64, 0, 8><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, w, ldw, c.slabs, c.its, wbytes, ibytes);
 #undef GTA_PF
+      } else if (grid) {
+        with_bools([&](auto BF) {
+          k_agg_h32<true, 3, false, true, BF(), true><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, w, ldw, c.slabs,
+                                                                                c.its, static_cast<uint32_t>(nnz));
+        }, bf);
       } else if (a1) h32(yes, IC<3>{}, no, yes);
       else if (w) h32(yes, IC<3>{}, no, no);
       else h32(no, IC<2>{}, no, no);
