@@ -2515,63 +2515,26 @@ k_aggregate_combine(PlanView plan, int F, const float* __restrict__ row_scale, f
 }
 
 // ---------------------------------------------------------------------------
-// K1 scatter: byte-exact row copies node -> edge, one wave per destination row
+// Shared pieces of the edge-wise / node-wise element kernels (K1, K3, K5) and
+// of the unfused GAT softmax (K3', k_softmax_shift)
 // ---------------------------------------------------------------------------
-template <typename UNIT>
-__global__ void __launch_bounds__(kBlock)
-k_scatter(int dir, const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
-          const UNIT* __restrict__ x, int64_t ldx_u, int64_t row_u, UNIT* __restrict__ out, int64_t ldo_u) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
-  if (row >= n_rows) return;
-  const int64_t eb = indptr[row], ee = indptr[row + 1];
-  const int64_t total = (ee - eb) * row_u;
-  for (int64_t t = lane; t < total; t += kWave) {
-    const int64_t el = t / row_u, c = t - el * row_u;
-    const int64_t e = eb + el;
-    const int64_t src = (dir == GTA_DIR_R) ? row : indices[e];
-    out[e * ldo_u + c] = x[src * ldx_u + c];
+// A wave-per-row kernel's prologue: lane, row and the row's edge range; false past the last row
+struct WaveRow {
+  int lane;
+  int64_t row, beg, end;
+  __device__ __forceinline__ bool init(const int64_t* __restrict__ indptr, int64_t n_rows) {
+    lane = threadIdx.x & (kWave - 1);
+    row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+    if (row >= n_rows) return false;
+    beg = indptr[row], end = indptr[row + 1];
+    return true;
   }
-}
+};
 
-// ---------------------------------------------------------------------------
-// K3 apply_edge / K5 apply_node: element-wise with head broadcast + SF
-// ---------------------------------------------------------------------------
+// k_apply_edge_cols keeps its own text: edge_row is its row rule; ld_vec reads VW columns for it and for Operand
 __device__ __forceinline__ int64_t edge_row(int mode, int64_t e, int64_t row, const int32_t* indices) {
   return mode == GTA_IDX_EDGE ? e : (mode == GTA_IDX_SRC ? static_cast<int64_t>(indices[e]) : row);
 }
-
-__global__ void __launch_bounds__(kBlock)
-k_apply_edge(int bin, int sf, const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
-             int64_t n_rows, const float* __restrict__ a, int a_mode, int64_t lda, int Fa,
-             const float* __restrict__ b, int b_mode, int64_t ldb, int Fb, float* __restrict__ out,
-             int64_t ldo, int Fo) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
-  if (row >= n_rows) return;
-  const int64_t eb = indptr[row], ee = indptr[row + 1];
-  const int64_t total = (ee - eb) * Fo;
-  const int ga = Fo / Fa, gb = (b != nullptr) ? Fo / Fb : 1;
-  for (int64_t t = lane; t < total; t += kWave) {
-    const int64_t el = t / Fo;
-    const int c = static_cast<int>(t - el * Fo);
-    const int64_t e = eb + el;
-    float va = a[edge_row(a_mode, e, row, indices) * lda + c / ga];
-    if (b != nullptr) {
-      const int64_t rb = (ldb == 0) ? 0 : edge_row(b_mode, e, row, indices);
-      va = bin_apply(bin, va, b[rb * ldb + c / gb]);
-    }
-    out[e * ldo + c] = sf_apply(sf, va);
-  }
-}
-
-// Row-sweep forms of K3 (the generic kernel above divides per element and re-reads
-// the index per element).  A wave owns a destination row and walks its edges:
-//  * k_apply_edge_cols: lanes cover the output columns, VW per lane (float4/float2
-//    when rows are aligned and any head broadcast keeps VW columns in one head),
-//    4 edges unrolled so their row gathers are in flight together;
-//  * k_apply_edge_pack: Fo <= 32 (a power of two): 64/Fo edges per wave instruction,
-//    lane = (edge slot, column).
 template <int VW>
 __device__ __forceinline__ void ld_vec(const float* p, float* v, int ga, int c) {  // VW output columns from c
   if (ga == 1) {
@@ -2585,6 +2548,120 @@ __device__ __forceinline__ void ld_vec(const float* p, float* v, int ga, int c) 
   }
 }
 
+
+// One operand of an element kernel: p[rows, ld] read by edge (EDGE), by the edge's source (SRC) or
+// by its destination row (DST); ld == 0 is one row for all (any row id times 0: the test below only
+// keeps such an operand from reading source ids); output column c reads column c / g.
+struct Operand {
+  const float* p;
+  int mode;
+  int64_t ld;
+  int g;
+  // the row of edge e, whose destination is dst and whose source is src() (called in mode SRC only)
+  template <class Src>
+  __device__ __forceinline__ const float* row(int64_t e, int64_t dst, Src src) const {
+    const int64_t r = mode == GTA_IDX_EDGE ? e : (mode == GTA_IDX_SRC ? (ld == 0 ? 0 : static_cast<int64_t>(src())) : dst);
+    return p + r * ld;
+  }
+  __device__ __forceinline__ bool reads(int m) const { return p != nullptr && ld != 0 && mode == m; }  // row() uses m's ids
+  __device__ __forceinline__ int col(int c) const { return c / g; }
+};
+
+// out = sf(bin(a, b)), or sf(a) without a b: the one combine of every K3 / K5 form
+template <int VW>
+__device__ __forceinline__ void combine(int bin, int sf, bool has_b, const Vec<VW>& va, const Vec<VW>& vb, Vec<VW>& out) {
+#pragma unroll
+  for (int q = 0; q < VW; ++q) out.v[q] = sf_apply(sf, has_b ? bin_apply(bin, va.v[q], vb.v[q]) : va.v[q]);
+}
+
+// The head-lane edge walk of a row (lane = k*H + h: edge slot k, head h): 64 indices per coalesced
+// load, a full chunk in H steps with its gathers of b issued NB at a time, the last chunk masked;
+// body(edge, b[src(edge), h]) once per edge and head, edges ascending per lane.  The full chunk
+// shuffles with ds_bpermute itself (byte address 4 * slot), its base pinned inside the chunk loop:
+// left loop-invariant every step's address gets a register of its own (79 VGPRs for 40 at H = 64).
+template <int H, class Body>
+__device__ __forceinline__ void head_lane_walk(int lane, int64_t beg, int64_t end, const int32_t* indices, const float* b,
+                                               int64_t ldb, Body body) {
+  constexpr int EPS = kWave / H;  // edges per step
+  constexpr int NB = H < 8 ? H : 8;
+  const int h = lane % H, k = lane / H;
+  for (int64_t e0 = beg; e0 < end; e0 += kWave) {
+    const int cnt = (end - e0 < kWave) ? static_cast<int>(end - e0) : kWave;
+    const int mine = (lane < cnt) ? indices[e0 + lane] : 0;
+    if (cnt == kWave) {  // H steps of EPS edges, gathers issued NB at a time
+      int base = 4 * k;
+      asm volatile("" : "+v"(base));  // the pin
+#pragma unroll
+      for (int j0 = 0; j0 < H; j0 += NB) {
+        float v[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const int src = __builtin_amdgcn_ds_bpermute(4 * (j0 + j) * EPS + base, mine);
+          v[j] = b[static_cast<int64_t>(src) * ldb + h];
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) body(e0 + (j0 + j) * EPS + k, v[j]);
+      }
+    } else {
+      for (int j = 0; j * EPS < cnt; ++j) {
+        const int slot = j * EPS + k;
+        const int src = __shfl(mine, slot < cnt ? slot : 0);
+        if (slot < cnt) body(e0 + slot, b[static_cast<int64_t>(src) * ldb + h]);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// K1 scatter: byte-exact row copies node -> edge, one wave per destination row
+// ---------------------------------------------------------------------------
+template <typename UNIT>
+__global__ void __launch_bounds__(kBlock)
+k_scatter(int dir, const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
+          const UNIT* __restrict__ x, int64_t ldx_u, int64_t row_u, UNIT* __restrict__ out, int64_t ldo_u) {
+  WaveRow w;
+  if (!w.init(indptr, n_rows)) return;
+  const int64_t total = (w.end - w.beg) * row_u;
+  for (int64_t t = w.lane; t < total; t += kWave) {
+    const int64_t el = t / row_u, c = t - el * row_u;
+    const int64_t e = w.beg + el;
+    const int64_t src = (dir == GTA_DIR_R) ? w.row : indices[e];
+    out[e * ldo_u + c] = x[src * ldx_u + c];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// K3 apply_edge / K5 apply_node: element-wise with head broadcast + SF
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock)
+k_apply_edge(int bin, int sf, const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+             int64_t n_rows, const float* __restrict__ a, int a_mode, int64_t lda, int Fa,
+             const float* __restrict__ b, int b_mode, int64_t ldb, int Fb, float* __restrict__ out,
+             int64_t ldo, int Fo) {
+  WaveRow w;
+  if (!w.init(indptr, n_rows)) return;
+  const int64_t total = (w.end - w.beg) * Fo;
+  const Operand A{a, a_mode, lda, Fo / Fa}, B{b, b_mode, ldb, (b != nullptr) ? Fo / Fb : 1};
+  for (int64_t t = w.lane; t < total; t += kWave) {
+    const int64_t el = t / Fo;
+    const int c = static_cast<int>(t - el * Fo);
+    const int64_t e = w.beg + el;
+    const auto src = [&] { return indices[e]; };
+    Vec<1> va, vb;
+    va.v[0] = A.row(e, w.row, src)[A.col(c)];
+    if (b != nullptr) vb.v[0] = B.row(e, w.row, src)[B.col(c)];
+    combine<1>(bin, sf, b != nullptr, va, vb, va);
+    out[e * ldo + c] = va.v[0];
+  }
+}
+
+// Row-sweep forms of K3 (the generic kernel above divides per element and re-reads
+// the index per element).  A wave owns a destination row and walks its edges:
+//  * k_apply_edge_cols: lanes cover the output columns, VW per lane (float4/float2
+//    when rows are aligned and any head broadcast keeps VW columns in one head),
+//    4 edges unrolled so their row gathers are in flight together;
+//  * k_apply_edge_pack: Fo <= 32 (a power of two): 64/Fo edges per wave instruction,
+//    lane = (edge slot, column).
 template <int VW>
 __global__ void __launch_bounds__(kBlock)
 k_apply_edge_cols(int bin, int sf, const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
@@ -2647,34 +2724,27 @@ k_apply_edge_flat(int bin, int sf, const int32_t* __restrict__ erow, const int32
   const int64_t e0 = (static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform()) * EPW;
   if (e0 >= nnz) return;
   const int n = static_cast<int>(min<int64_t>(EPW, nnz - e0));
-  const bool need_src = a_mode == GTA_IDX_SRC || (b != nullptr && ldb != 0 && b_mode == GTA_IDX_SRC);
-  const bool need_dst = a_mode == GTA_IDX_DST || (b != nullptr && ldb != 0 && b_mode == GTA_IDX_DST);
-  const int src = (need_src && lane < n) ? indices[e0 + lane] : 0;
-  const int dst = (need_dst && lane < n) ? erow[e0 + lane] : 0;
-  auto rowof = [&](int mode, int k) -> int64_t {  // k: uniform edge slot of this chunk
-    return mode == GTA_IDX_EDGE ? e0 + k
-                                : static_cast<int64_t>(__builtin_amdgcn_readlane(mode == GTA_IDX_SRC ? src : dst, k));
-  };
+  const Operand A{a, a_mode, lda, ga}, B{b, b_mode, ldb, gb};
+  const int src = ((A.reads(GTA_IDX_SRC) || B.reads(GTA_IDX_SRC)) && lane < n) ? indices[e0 + lane] : 0;
+  const int dst = ((A.reads(GTA_IDX_DST) || B.reads(GTA_IDX_DST)) && lane < n) ? erow[e0 + lane] : 0;
   const int c = lane * VW;
   for (int u0 = 0; u0 < n; u0 += U) {
-    float va[U][VW], vb[U][VW];
+    Vec<VW> va[U], vb[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      if (u0 + u < n) {
-        ld_vec<VW>(a + rowof(a_mode, u0 + u) * lda, va[u], ga, c);
-        if (b != nullptr) ld_vec<VW>(b + (ldb == 0 ? 0 : rowof(b_mode, u0 + u)) * ldb, vb[u], gb, c);
+      if (u0 + u < n) {  // u0 + u: uniform edge slot of this chunk, so every row id is a uniform value
+        const int64_t d = __builtin_amdgcn_readlane(dst, u0 + u);
+        const auto s = [&] { return __builtin_amdgcn_readlane(src, u0 + u); };
+        ld_vec<VW>(A.row(e0 + u0 + u, d, s), va[u].v, A.g, c);
+        if (b != nullptr) ld_vec<VW>(B.row(e0 + u0 + u, d, s), vb[u].v, B.g, c);
       }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (u0 + u < n) {
-        float o[VW];
-#pragma unroll
-        for (int q = 0; q < VW; ++q) o[q] = sf_apply(sf, b != nullptr ? bin_apply(bin, va[u][q], vb[u][q]) : va[u][q]);
-        float* op = out + (e0 + u0 + u) * ldo + c;
-        if (VW == 4) *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
-        else if (VW == 2) *reinterpret_cast<float2*>(op) = make_float2(o[0], o[1]);
-        else op[0] = o[0];
+        Vec<VW> o;
+        combine<VW>(bin, sf, b != nullptr, va[u], vb[u], o);
+        o.store(out + (e0 + u0 + u) * ldo + c);
       }
     }
   }
@@ -2685,18 +2755,20 @@ k_apply_edge_pack(int bin, int sf, const int64_t* __restrict__ indptr, const int
                   int64_t n_rows, const float* __restrict__ a, int a_mode, int64_t lda, int ga,
                   const float* __restrict__ b, int b_mode, int64_t ldb, int gb, float* __restrict__ out,
                   int64_t ldo, int Fo) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
-  if (row >= n_rows) return;
-  const int64_t eb = indptr[row], ee = indptr[row + 1];
-  const int epi = kWave / Fo, k = lane / Fo, c = lane - k * Fo;
-  const int ca = c / ga, cb = c / gb;
-  for (int64_t e0 = eb; e0 < ee; e0 += epi) {
+  WaveRow w;
+  if (!w.init(indptr, n_rows)) return;
+  const Operand A{a, a_mode, lda, ga}, B{b, b_mode, ldb, gb};
+  const int epi = kWave / Fo, k = w.lane / Fo, c = w.lane - k * Fo;
+  const int ca = A.col(c), cb = B.col(c);
+  for (int64_t e0 = w.beg; e0 < w.end; e0 += epi) {
     const int64_t e = e0 + k;
-    if (e < ee) {
-      float v = a[edge_row(a_mode, e, row, indices) * lda + ca];
-      if (b != nullptr) v = bin_apply(bin, v, b[((ldb == 0) ? 0 : edge_row(b_mode, e, row, indices)) * ldb + cb]);
-      out[e * ldo + c] = sf_apply(sf, v);
+    if (e < w.end) {
+      const auto src = [&] { return indices[e]; };
+      Vec<1> va, vb;
+      va.v[0] = A.row(e, w.row, src)[ca];
+      if (b != nullptr) vb.v[0] = B.row(e, w.row, src)[cb];
+      combine<1>(bin, sf, b != nullptr, va, vb, va);
+      out[e * ldo + c] = va.v[0];
     }
   }
 }
@@ -2727,20 +2799,17 @@ k_apply_node4(int bin, int sf, uint32_t n4, uint32_t F4, const TA* __restrict__ 
               const float* __restrict__ b, int64_t ldb, float* __restrict__ out, int64_t ldo) {
   for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n4; t += gridDim.x * blockDim.x) {
     const uint32_t i = t / F4, c = (t - i * F4) * 4u;
-    Vec<4> av;
-    load_row(av, a + i * lda + c);
-    float4 v = make_float4(av.v[0], av.v[1], av.v[2], av.v[3]);
+    Vec<4> va, vb;
+    load_row(va, a + i * lda + c);
     if (BM == 1) {
-      const float4 w = *reinterpret_cast<const float4*>(b + i * ldb + c);
-      v.x = bin_apply(bin, v.x, w.x); v.y = bin_apply(bin, v.y, w.y);
-      v.z = bin_apply(bin, v.z, w.z); v.w = bin_apply(bin, v.w, w.w);
+      vb.load(b + i * ldb + c);
     } else if (BM == 2) {
-      const float w = b[i * ldb];
-      v.x = bin_apply(bin, v.x, w); v.y = bin_apply(bin, v.y, w);
-      v.z = bin_apply(bin, v.z, w); v.w = bin_apply(bin, v.w, w);
+      const float t = b[i * ldb];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) vb.v[q] = t;
     }
-    v.x = sf_apply(sf, v.x); v.y = sf_apply(sf, v.y); v.z = sf_apply(sf, v.z); v.w = sf_apply(sf, v.w);
-    *reinterpret_cast<float4*>(out + i * ldo + c) = v;
+    combine<4>(bin, sf, BM != 0, va, vb, va);
+    va.store(out + i * ldo + c);
   }
 }
 
@@ -2760,8 +2829,6 @@ k_edge_softmax(const int64_t* __restrict__ indptr, const int32_t* __restrict__ i
                const float* __restrict__ a, int64_t lda, const float* __restrict__ b, int64_t ldb, int sf,
                int normalize, float* __restrict__ out, float* __restrict__ sums,
                const float* __restrict__ shift = nullptr) {
-  constexpr int EPS = kWave / H;  // edges per step
-  constexpr int NB = H < 8 ? H : 8;
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
   if (row >= n_rows) return;
@@ -2772,48 +2839,16 @@ k_edge_softmax(const int64_t* __restrict__ indptr, const int32_t* __restrict__ i
   float s = 0.f;
   for (int pass = 0; pass < 2; ++pass) {
     const float inv = s;  // pass 1: row sum (division below, not a reciprocal)
-    for (int64_t e0 = beg; e0 < end; e0 += kWave) {
-      const int cnt = (end - e0 < kWave) ? static_cast<int>(end - e0) : kWave;
-      const int mine = (lane < cnt) ? indices[e0 + lane] : 0;
-      if (cnt == kWave) {  // H steps of EPS edges, gathers issued NB at a time
-#pragma unroll
-        for (int j0 = 0; j0 < H; j0 += NB) {
-          float v[NB];
-#pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            const int src = __shfl(mine, (j0 + j) * EPS + k);
-            v[j] = b[static_cast<int64_t>(src) * ldb + h];
-          }
-#pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            const float x = SH ? sf_shift(sf, ar + v[j], mr) : sf_apply(sf, ar + v[j]);
-            float* o = out + (e0 + (j0 + j) * EPS + k) * H + h;
-            if (pass == 0) {
-              s += x;
-              if (!normalize) *o = x;
-            } else {
-              *o = x / inv;
-            }
-          }
-        }
+    head_lane_walk<H>(lane, beg, end, indices, b, ldb, [&](int64_t e, float bv) __attribute__((always_inline)) {
+      const float x = SH ? sf_shift(sf, ar + bv, mr) : sf_apply(sf, ar + bv);
+      float* o = out + e * H + h;
+      if (pass == 0) {
+        s += x;
+        if (!normalize) *o = x;
       } else {
-        for (int j = 0; j * EPS < cnt; ++j) {
-          const int slot = j * EPS + k;
-          const int src = __shfl(mine, slot < cnt ? slot : 0);
-          if (slot < cnt) {
-            const float bv = b[static_cast<int64_t>(src) * ldb + h];
-            const float x = SH ? sf_shift(sf, ar + bv, mr) : sf_apply(sf, ar + bv);
-            float* o = out + (e0 + slot) * H + h;
-            if (pass == 0) {
-              s += x;
-              if (!normalize) *o = x;
-            } else {
-              *o = x / inv;
-            }
-          }
-        }
+        *o = x / inv;
       }
-    }
+    });
     if (pass == 0) {
 #pragma unroll
       for (int off = H; off < kWave; off <<= 1) s += __shfl_xor(s, off);
@@ -2836,10 +2871,10 @@ k_edge_softmax_v(const int64_t* __restrict__ indptr, const int32_t* __restrict__
                  int normalize, float* __restrict__ out, float* __restrict__ sums,
                  const float* __restrict__ shift = nullptr) {
   constexpr int Q = H / 4;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
-  if (row >= n_rows) return;
-  const int64_t beg = indptr[row], end = indptr[row + 1];
+  WaveRow w;
+  if (!w.init(indptr, n_rows)) return;
+  const int lane = w.lane;
+  const int64_t row = w.row, beg = w.beg, end = w.end;
   float ar[H], s[H], mr[SH ? H : 1];
 #pragma unroll
   for (int h = 0; h < H; ++h) {
@@ -2868,27 +2903,28 @@ k_edge_softmax_v(const int64_t* __restrict__ indptr, const int32_t* __restrict__
     }
     return ok;
   };
+  const auto chunk = [&](int64_t e0) { return reinterpret_cast<float4*>(out + (e0 + lane) * H); };  // this lane's edge
+  const auto put = [&](int64_t e0, const float4 (&v)[Q]) {
+    float4* o = chunk(e0);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) o[q] = v[q];
+  };
+  const auto div4 = [&](float4 v, int q) {  // v / s for heads 4q .. 4q + 3
+    return make_float4(v.x / s[4 * q], v.y / s[4 * q + 1], v.z / s[4 * q + 2], v.w / s[4 * q + 3]);
+  };
   // pass 1
   int64_t e0 = beg;
 #pragma unroll
   for (int c = 0; c < K; ++c) {
     if (e0 < end) {
       const bool ok = visit(e0, keep[c]);
-      if (!normalize && ok) {
-        float4* o = reinterpret_cast<float4*>(out + (e0 + lane) * H);
-#pragma unroll
-        for (int q = 0; q < Q; ++q) o[q] = keep[c][q];
-      }
+      if (!normalize && ok) put(e0, keep[c]);
     }
     e0 += kWave;
   }
   for (int64_t f0 = beg + K * kWave; f0 < end; f0 += kWave) {
     float4 v[Q];
-    if (visit(f0, v)) {
-      float4* o = reinterpret_cast<float4*>(out + (f0 + lane) * H);
-#pragma unroll
-      for (int q = 0; q < Q; ++q) o[q] = v[q];
-    }
+    if (visit(f0, v)) put(f0, v);
   }
 #pragma unroll
   for (int h = 0; h < H; ++h) {
@@ -2907,22 +2943,17 @@ k_edge_softmax_v(const int64_t* __restrict__ indptr, const int32_t* __restrict__
 #pragma unroll
   for (int c = 0; c < K; ++c) {
     if (e0 + lane < end) {
-      float4* o = reinterpret_cast<float4*>(out + (e0 + lane) * H);
 #pragma unroll
-      for (int q = 0; q < Q; ++q)
-        o[q] = make_float4(keep[c][q].x / s[4 * q], keep[c][q].y / s[4 * q + 1], keep[c][q].z / s[4 * q + 2],
-                           keep[c][q].w / s[4 * q + 3]);
+      for (int q = 0; q < Q; ++q) keep[c][q] = div4(keep[c][q], q);
+      put(e0, keep[c]);
     }
     e0 += kWave;
   }
   for (int64_t f0 = beg + K * kWave; f0 < end; f0 += kWave) {
     if (f0 + lane < end) {
-      float4* o = reinterpret_cast<float4*>(out + (f0 + lane) * H);
+      float4* o = chunk(f0);
 #pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const float4 v = o[q];
-        o[q] = make_float4(v.x / s[4 * q], v.y / s[4 * q + 1], v.z / s[4 * q + 2], v.w / s[4 * q + 3]);
-      }
+      for (int q = 0; q < Q; ++q) o[q] = div4(o[q], q);
     }
   }
 }
@@ -2939,40 +2970,15 @@ __global__ void __launch_bounds__(kBlock)
 k_softmax_shift(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows,
                 const float* __restrict__ a, int64_t lda, const float* __restrict__ b, int64_t ldb, int sf,
                 float* __restrict__ shift) {
-  constexpr int EPS = kWave / H;  // edges per step
-  constexpr int NB = H < 8 ? H : 8;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
-  if (row >= n_rows) return;
-  const int h = lane % H, k = lane / H;
-  const int64_t beg = indptr[row], end = indptr[row + 1];
+  WaveRow w;
+  if (!w.init(indptr, n_rows)) return;
+  const int h = w.lane % H, k = w.lane / H;
   float m = -INFINITY;
-  for (int64_t e0 = beg; e0 < end; e0 += kWave) {
-    const int cnt = (end - e0 < kWave) ? static_cast<int>(end - e0) : kWave;
-    const int mine = (lane < cnt) ? indices[e0 + lane] : 0;
-    if (cnt == kWave) {
-#pragma unroll
-      for (int j0 = 0; j0 < H; j0 += NB) {
-        float v[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          const int src = __shfl(mine, (j0 + j) * EPS + k);
-          v[j] = b[static_cast<int64_t>(src) * ldb + h];
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) m = red_max(m, v[j]);
-      }
-    } else {
-      for (int j = 0; j * EPS < cnt; ++j) {
-        const int slot = j * EPS + k;
-        const int src = __shfl(mine, slot < cnt ? slot : 0);
-        if (slot < cnt) m = red_max(m, b[static_cast<int64_t>(src) * ldb + h]);
-      }
-    }
-  }
+  head_lane_walk<H>(w.lane, w.beg, w.end, indices, b, ldb,
+                    [&](int64_t, float bv) __attribute__((always_inline)) { m = red_max(m, bv); });
 #pragma unroll
   for (int off = H; off < kWave; off <<= 1) m = red_max(m, __shfl_xor(m, off));
-  if (k == 0) shift[row * H + h] = (end > beg) ? sf_g(sf, a[row * lda + h] + m) : 0.f;
+  if (k == 0) shift[w.row * H + h] = (w.end > w.beg) ? sf_g(sf, a[w.row * lda + h] + m) : 0.f;
 }
 
 // ---------------------------------------------------------------------------
@@ -5106,12 +5112,49 @@ void with_bools(Fn fn, bool b, Rest... rest) {
   else with_bools([&](auto... cs) { fn(BC<false>{}, cs...); }, rest...);
 }
 
-// The ordered reduce's ladder (k_seg_reduce, k_seg_reduce_red, k_seg_reduce_att): fn(VW), VW = F / 64
+// The vector-width ladder fn(IC<VW>), VW in 1, 2, 4: k_seg_reduce* (F / 64), k_apply_edge_cols / _flat (vec_ok)
 template <class Fn>
-void launch_seg_reduce(int vw, Fn fn) {
+void dispatch_vw(int vw, Fn fn) {
   if (vw == 2) fn(IC<2>{});
   else if (vw == 4) fn(IC<4>{});
   else fn(IC<1>{});
+}
+
+// The heads ladder of the unfused softmax kernels: fn(IC<H>), heads a power of two in 1 .. 64 (check_heads)
+template <class Fn>
+void dispatch_heads(int64_t heads, Fn fn) {
+  switch (heads) {
+    case 1: return fn(IC<1>{});
+    case 2: return fn(IC<2>{});
+    case 4: return fn(IC<4>{});
+    case 8: return fn(IC<8>{});
+    case 16: return fn(IC<16>{});
+    case 32: return fn(IC<32>{});
+    case 64: return fn(IC<64>{});
+  }
+}
+
+// One wave per row, kWavesPerBlock rows per block
+inline dim3 row_grid(int64_t n_rows) { return dim3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock)); }
+
+// May a K3 kernel move vw floats per lane?  out and each full-width operand (g == 1) vw-float aligned,
+// a head-broadcast operand with vw output columns in one head.  ops._flat_aligned mirrors this in Python.
+bool vec_ok(int vw, const float* a, int64_t lda, int ga, const float* b, int64_t ldb, int gb, const float* out,
+            int64_t ldo) {
+  if (ldo % vw || !aligned(out, 4 * vw)) return false;
+  if (ga == 1 ? (lda % vw || !aligned(a, 4 * vw)) : (ga % vw != 0)) return false;
+  if (b && (gb == 1 ? (ldb % vw || !aligned(b, 4 * vw)) : (gb % vw != 0))) return false;
+  return true;
+}
+
+// The heads / sf / leading-dimension checks of gta_edge_softmax* and gta_softmax_shift; 0 or the error code
+int check_heads(const char* who, int64_t heads, int sf, bool need_exp, int64_t lda, int64_t ldb) {
+  if (heads <= 0 || heads > kWave || (heads & (heads - 1)))
+    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": heads must be a power of two <= 64");
+  if (need_exp && !sf_is_exp_form(sf))
+    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": sf must be EXP_LEAKY_RELU or EXP");
+  if (lda < heads || ldb < heads) return fail(GTA_ERR_ARG, std::string(who) + ": leading dimension < heads");
+  return GTA_OK;
 }
 }  // namespace
 extern "C" {
@@ -5210,7 +5253,7 @@ int gta_aggregate_blocked_plan_build(const int64_t* indptr, const int32_t* indic
                            reinterpret_cast<char*>(v.row_items) - static_cast<char*>(plan), row_edges, class_major};
   GTA_HIP(hipMemcpyAsync(v.hdr, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
   GTA_HIP(hipMemsetAsync(v.bucket, 0, 2 * 256 * 4, s));
-  k_blocked_seg<<<dim3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s>>>(
+  k_blocked_seg<<<row_grid(n_rows), dim3(kBlock), 0, s>>>(
       indptr, indices, n_rows, B, bsize, item_edges, row_edges, class_major, v);
   GTA_LAUNCHED("k_blocked_seg");
   k_blocked_scan<<<1, 64, 0, s>>>(v, B, class_major);
@@ -5363,7 +5406,7 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
     GTA_LAUNCHED("k_agg_seg2d");
   }
   if (phase == 1) return GTA_OK;  // the item launch only; a later phase-2 call reduces
-  launch_seg_reduce(vw, [&](auto V) {
+  dispatch_vw(vw, [&](auto V) {
     k_seg_reduce<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, row_scale, y, ldy, accumulate, c.ri);
   });
   GTA_LAUNCHED("k_seg_reduce");
@@ -5443,7 +5486,7 @@ int gta_reduce_blocked(int red, const int64_t* indptr, const int32_t* indices, i
     else seg4(IC<16>{}, IC<2>{}, IC<16>{}, c.g4);
     GTA_LAUNCHED("k_red_seg4");
   }
-  launch_seg_reduce(vw, [&](auto V) {
+  dispatch_vw(vw, [&](auto V) {
     k_seg_reduce_red<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, sbit, y, ldy, c.ri);
   });
   GTA_LAUNCHED("k_seg_reduce_red");
@@ -5526,7 +5569,7 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
     GTA_LAUNCHED("k_agg_seg4<att>");
   }
   const int H = static_cast<int>(heads);
-  launch_seg_reduce(static_cast<int>(F / 64), [&](auto V) {  // skip_single is set at F = 128 only
+  dispatch_vw(static_cast<int>(F / 64), [&](auto V) {  // skip_single is set at F = 128 only
     k_seg_reduce_att<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, H, normalize, y, ldy, sums, c.ri, skip_single, sf_out);
   });
   GTA_LAUNCHED("k_seg_reduce_att");
@@ -5780,25 +5823,17 @@ int gta_scatter(int dir, const int64_t* indptr, const int32_t* indices, int64_t 
   const int64_t rowb = F * esz, ldxb = ldx * esz, ldob = ldo * esz;
   int unit = 16;
   while (unit > 2 && (rowb % unit || ldxb % unit || ldob % unit || !aligned(x, unit) || !aligned(out, unit))) unit >>= 1;
-  const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock)), blk(kBlock);
-  hipStream_t s = S(stream);
-  switch (unit) {
-    case 16:
-      k_scatter<uint4><<<grid, blk, 0, s>>>(dir, indptr, indices, n_rows, static_cast<const uint4*>(x), ldxb / 16,
-                                            rowb / 16, static_cast<uint4*>(out), ldob / 16);
-      break;
-    case 8:
-      k_scatter<uint2><<<grid, blk, 0, s>>>(dir, indptr, indices, n_rows, static_cast<const uint2*>(x), ldxb / 8,
-                                            rowb / 8, static_cast<uint2*>(out), ldob / 8);
-      break;
-    case 4:
-      k_scatter<uint32_t><<<grid, blk, 0, s>>>(dir, indptr, indices, n_rows, static_cast<const uint32_t*>(x),
-                                               ldxb / 4, rowb / 4, static_cast<uint32_t*>(out), ldob / 4);
-      break;
-    default:
-      k_scatter<uint16_t><<<grid, blk, 0, s>>>(dir, indptr, indices, n_rows, static_cast<const uint16_t*>(x),
-                                               ldxb / 2, rowb / 2, static_cast<uint16_t*>(out), ldob / 2);
-  }
+  const auto launch = [&](auto u) {  // u: a value of the copy unit's type
+    using UNIT = decltype(u);
+    constexpr int64_t ub = sizeof(UNIT);
+    k_scatter<UNIT><<<row_grid(n_rows), dim3(kBlock), 0, S(stream)>>>(dir, indptr, indices, n_rows,
+                                                                      static_cast<const UNIT*>(x), ldxb / ub, rowb / ub,
+                                                                      static_cast<UNIT*>(out), ldob / ub);
+  };
+  if (unit == 16) launch(uint4{});
+  else if (unit == 8) launch(uint2{});
+  else if (unit == 4) launch(uint32_t{});
+  else launch(uint16_t{});
   GTA_LAUNCHED("k_scatter");
   return GTA_OK;
 }
@@ -5822,8 +5857,7 @@ int gta_apply_edge(int bin, int sf, const int64_t* indptr, const int32_t* indice
     return fail(GTA_ERR_ARG, "apply_edge: SRC operand needs indices");
   int64_t Fo;
   if (check_bcast(Fa, Fb, b != nullptr, &Fo)) return fail(GTA_ERR_ARG, "apply_edge: widths must divide");
-  if (n_rows == 0 || nnz == 0) return GTA_OK;
-  const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
+  const dim3 grid = row_grid(n_rows);
   const int fo = static_cast<int>(Fo), ga = static_cast<int>(Fo / Fa), gb = b ? static_cast<int>(Fo / Fb) : 1;
   if (tuning().apply_edge_form == 0) {
     k_apply_edge<<<grid, dim3(kBlock), 0, S(stream)>>>(bin, sf, indptr, indices, n_rows, a, a_mode, lda,
@@ -5833,21 +5867,13 @@ int gta_apply_edge(int bin, int sf, const int64_t* indptr, const int32_t* indice
     k_apply_edge_pack<<<grid, dim3(kBlock), 0, S(stream)>>>(bin, sf, indptr, indices, n_rows, a, a_mode, lda, ga,
                                                             b, b_mode, ldb, gb, out, ldo, fo);
   } else {
-    auto vec_ok = [&](int vw) {
-      if (fo % vw || ldo % vw || !aligned(out, 4 * vw)) return false;
-      if (ga == 1 ? (lda % vw || !aligned(a, 4 * vw)) : (ga % vw != 0)) return false;
-      if (b && (gb == 1 ? (ldb % vw || !aligned(b, 4 * vw)) : (gb % vw != 0))) return false;
-      return true;
-    };
-    if (vec_ok(4) && fo >= 4 * kWave)
-      k_apply_edge_cols<4><<<grid, dim3(kBlock), 0, S(stream)>>>(bin, sf, indptr, indices, n_rows, a, a_mode, lda, ga,
-                                                                 b, b_mode, ldb, gb, out, ldo, fo);
-    else if (vec_ok(2) && fo >= 2 * kWave)
-      k_apply_edge_cols<2><<<grid, dim3(kBlock), 0, S(stream)>>>(bin, sf, indptr, indices, n_rows, a, a_mode, lda, ga,
-                                                                 b, b_mode, ldb, gb, out, ldo, fo);
-    else
-      k_apply_edge_cols<1><<<grid, dim3(kBlock), 0, S(stream)>>>(bin, sf, indptr, indices, n_rows, a, a_mode, lda, ga,
-                                                                 b, b_mode, ldb, gb, out, ldo, fo);
+    int vw = 1;  // the widest of 4, 2 that divides fo, fills a wave and is aligned
+    for (int c : {2, 4})
+      if (fo % c == 0 && fo >= c * kWave && vec_ok(c, a, lda, ga, b, ldb, gb, out, ldo)) vw = c;
+    dispatch_vw(vw, [&](auto V) {
+      k_apply_edge_cols<V.value><<<grid, dim3(kBlock), 0, S(stream)>>>(bin, sf, indptr, indices, n_rows, a, a_mode, lda,
+                                                                       ga, b, b_mode, ldb, gb, out, ldo, fo);
+    });
   }
   GTA_LAUNCHED("k_apply_edge");
   return GTA_OK;
@@ -5871,20 +5897,13 @@ int gta_apply_edge_flat(int bin, int sf, const int32_t* edge_rows, const int32_t
   int vw = 0;
   for (int c : {4, 2, 1})
     if (Fo == static_cast<int64_t>(kWave) * c) vw = c;
-  auto vec_ok = [&](int w) {
-    if (ldo % w || !aligned(out, 4 * w)) return false;
-    if (ga == 1 ? (lda % w || !aligned(a, 4 * w)) : (ga % w != 0)) return false;
-    if (b && (gb == 1 ? (ldb % w || !aligned(b, 4 * w)) : (gb % w != 0))) return false;
-    return true;
-  };
-  if (!vw || !vec_ok(vw))
+  if (!vw || !vec_ok(vw, a, lda, ga, b, ldb, gb, out, ldo))
     return fail(GTA_ERR_UNSUPPORTED, "apply_edge_flat: the output must be 64, 128 or 256 columns, rows aligned to them");
   const dim3 grid(static_cast<unsigned>((nnz + 32 * kWavesPerBlock - 1) / (32 * kWavesPerBlock)));
-#define GTA_AEF(VW_)                                                                                             \
-  k_apply_edge_flat<VW_><<<grid, dim3(kBlock), 0, S(stream)>>>(bin, sf, edge_rows, indices, nnz, a, a_mode, lda, ga, \
-                                                              b, b_mode, ldb, gb, out, ldo)
-  if (vw == 4) GTA_AEF(4); else if (vw == 2) GTA_AEF(2); else GTA_AEF(1);
-#undef GTA_AEF
+  dispatch_vw(vw, [&](auto V) {
+    k_apply_edge_flat<V.value><<<grid, dim3(kBlock), 0, S(stream)>>>(bin, sf, edge_rows, indices, nnz, a, a_mode, lda,
+                                                                     ga, b, b_mode, ldb, gb, out, ldo);
+  });
   GTA_LAUNCHED("k_apply_edge_flat");
   return GTA_OK;
 }
@@ -5901,18 +5920,19 @@ int gta_apply_node(int bin, int sf, int64_t n, const void* a, int64_t lda, int64
   const uint16_t* ah = static_cast<const uint16_t*>(a);
   int64_t Fo;
   if (check_bcast(Fa, Fb, b != nullptr, &Fo)) return fail(GTA_ERR_ARG, "apply_node: widths must divide");
-  if (n == 0) return GTA_OK;
   const int64_t total = n * Fo;
   const int bm = !b ? 0 : (Fb == Fo ? 1 : (Fb == 1 ? 2 : -1));
   if (tuning().apply_node_vec && bm >= 0 && Fa == Fo && Fo % 4 == 0 && total / 4 < (int64_t(1) << 32) && lda % 4 == 0 &&
       ldo % 4 == 0 && aligned(a, bf ? 8 : 16) && aligned(out, 16) && (bm != 1 || (ldb % 4 == 0 && aligned(b, 16)))) {
     const uint32_t n4 = static_cast<uint32_t>(total / 4), F4 = static_cast<uint32_t>(Fo / 4);
     const dim3 g(static_cast<unsigned>(std::min<int64_t>((n4 + kBlock - 1) / kBlock, 256 * 16))), blk(kBlock);
-#define GTA_AN4(BM_)                                                                                     \
-  if (bf) k_apply_node4<BM_, uint16_t><<<g, blk, 0, S(stream)>>>(bin, sf, n4, F4, ah, lda, b, ldb, out, ldo); \
-  else k_apply_node4<BM_><<<g, blk, 0, S(stream)>>>(bin, sf, n4, F4, af, lda, b, ldb, out, ldo)
-    if (bm == 0) { GTA_AN4(0); } else if (bm == 1) { GTA_AN4(1); } else { GTA_AN4(2); }
-#undef GTA_AN4
+    const auto launch = [&](auto BM) {
+      if (bf) k_apply_node4<BM.value, uint16_t><<<g, blk, 0, S(stream)>>>(bin, sf, n4, F4, ah, lda, b, ldb, out, ldo);
+      else k_apply_node4<BM.value><<<g, blk, 0, S(stream)>>>(bin, sf, n4, F4, af, lda, b, ldb, out, ldo);
+    };
+    if (bm == 0) launch(IC<0>{});
+    else if (bm == 1) launch(IC<1>{});
+    else launch(IC<2>{});
     GTA_LAUNCHED("k_apply_node4");
     return GTA_OK;
   }
@@ -5937,44 +5957,31 @@ static int edge_softmax_impl(const char* who, bool shifted, const int64_t* indpt
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
   if (!indptr || !a_dst || !b_src || n_rows < 0 || nnz < 0 || (nnz > 0 && (!indices || !out)) || (shifted && !shift))
     return fail(GTA_ERR_ARG, std::string(who) + ": bad arguments");
-  if (heads <= 0 || heads > kWave || (heads & (heads - 1)))
-    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": heads must be a power of two <= 64");
-  if (shifted && !sf_is_exp_form(sf))
-    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": sf must be EXP_LEAKY_RELU or EXP");
-  if (lda < heads || ldb < heads) return fail(GTA_ERR_ARG, std::string(who) + ": leading dimension < heads");
+  if (const int rc = check_heads(who, heads, sf, shifted, lda, ldb)) return rc;
   if (n_rows == 0) return GTA_OK;
-  const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
+  const dim3 grid = row_grid(n_rows);
   const bool vec = tuning().esm_lane && (heads == 4 || heads == 8 || heads == 16) && ldb % 4 == 0 && aligned(b_src, 16) &&
                    (nnz == 0 || aligned(out, 16));
   if (vec) {
-#define GTA_ESMV(H_, K_)                                                                                          \
-  if (shifted)                                                                                                    \
-    k_edge_softmax_v<H_, K_, true><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda,     \
-                                                                         b_src, ldb, sf, normalize, out, sums,    \
-                                                                         shift);                                  \
-  else                                                                                                            \
-    k_edge_softmax_v<H_, K_><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src,    \
-                                                                   ldb, sf, normalize, out, sums)
     // chunks of 64 edges held in VGPRs: 4 for H <= 8, 2 at H = 16 (register budget)
-    if (heads == 4) { GTA_ESMV(4, 4); } else if (heads == 8) { GTA_ESMV(8, 4); } else { GTA_ESMV(16, 2); }
-#undef GTA_ESMV
+    const auto launch = [&](auto H, auto K) {
+      with_bools([&](auto SH) {
+        k_edge_softmax_v<H.value, K.value, SH.value><<<grid, dim3(kBlock), 0, S(stream)>>>(
+            indptr, indices, n_rows, a_dst, lda, b_src, ldb, sf, normalize, out, sums, shift);
+      }, shifted);
+    };
+    if (heads == 4) launch(IC<4>{}, IC<4>{});
+    else if (heads == 8) launch(IC<8>{}, IC<4>{});
+    else launch(IC<16>{}, IC<2>{});
     GTA_LAUNCHED("k_edge_softmax_v");
     return GTA_OK;
   }
-  switch (heads) {
-#define GTA_ESM(H_)                                                                                         \
-  case H_:                                                                                                  \
-    if (shifted)                                                                                            \
-      k_edge_softmax<H_, true><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda,   \
-                                                                     b_src, ldb, sf, normalize, out, sums,  \
-                                                                     shift);                                \
-    else                                                                                                    \
-      k_edge_softmax<H_><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src,  \
-                                                               ldb, sf, normalize, out, sums);              \
-    break;
-    GTA_ESM(1) GTA_ESM(2) GTA_ESM(4) GTA_ESM(8) GTA_ESM(16) GTA_ESM(32) GTA_ESM(64)
-#undef GTA_ESM
-  }
+  dispatch_heads(heads, [&](auto H) {
+    with_bools([&](auto SH) {
+      k_edge_softmax<H.value, SH.value><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src,
+                                                                              ldb, sf, normalize, out, sums, shift);
+    }, shifted);
+  });
   GTA_LAUNCHED("k_edge_softmax");
   return GTA_OK;
 }
@@ -5998,22 +6005,13 @@ int gta_softmax_shift(const int64_t* indptr, const int32_t* indices, int64_t n_r
                       void* stream) {
   if (!indptr || !a_dst || !shift || n_rows < 0 || nnz < 0 || (nnz > 0 && (!indices || !b_src)))
     return fail(GTA_ERR_ARG, "softmax_shift: bad arguments");
-  if (heads <= 0 || heads > kWave || (heads & (heads - 1)))
-    return fail(GTA_ERR_UNSUPPORTED, "softmax_shift: heads must be a power of two <= 64");
-  if (!sf_is_exp_form(sf)) return fail(GTA_ERR_UNSUPPORTED, "softmax_shift: sf must be EXP_LEAKY_RELU or EXP");
-  if (lda < heads || ldb < heads) return fail(GTA_ERR_ARG, "softmax_shift: leading dimension < heads");
+  if (const int rc = check_heads("softmax_shift", heads, sf, true, lda, ldb)) return rc;
   if (n_rows == 0) return GTA_OK;
   // nnz == 0: every degree is 0, the kernel writes zeros and reads neither indices nor b_src
-  const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
-  switch (heads) {
-#define GTA_SSH(H_)                                                                                          \
-  case H_:                                                                                                   \
-    k_softmax_shift<H_><<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src, ldb, \
-                                                              sf, shift);                                    \
-    break;
-    GTA_SSH(1) GTA_SSH(2) GTA_SSH(4) GTA_SSH(8) GTA_SSH(16) GTA_SSH(32) GTA_SSH(64)
-#undef GTA_SSH
-  }
+  dispatch_heads(heads, [&](auto H) {
+    k_softmax_shift<H.value><<<row_grid(n_rows), dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, a_dst, lda, b_src,
+                                                                              ldb, sf, shift);
+  });
   GTA_LAUNCHED("k_softmax_shift");
   return GTA_OK;
 }
@@ -6421,7 +6419,7 @@ int gta_tile_nnz(const int64_t* indptr, const int32_t* indices, int64_t n_rows, 
   if (!indptr || !counts || n_rows < 0 || n_cols <= 0 || T <= 0)
     return fail(GTA_ERR_ARG, "tile_nnz: bad arguments");
   if (n_rows == 0) return GTA_OK;
-  const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
+  const dim3 grid = row_grid(n_rows);
   k_tile_nnz<<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, indices, n_rows, n_cols, T, counts);
   GTA_LAUNCHED("k_tile_nnz");
   return GTA_OK;
@@ -6434,7 +6432,7 @@ int gta_synth_alpha(const int64_t* indptr, const int64_t* gen, int64_t n_rows, i
     return fail(GTA_ERR_ARG, "synth_alpha: bad arguments (heads must divide 64)");
   if (n_rows == 0 || nnz == 0) return GTA_OK;
   const uint32_t s1 = static_cast<uint32_t>(2 * logit_stream), s2 = s1 + 1u;
-  const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
+  const dim3 grid = row_grid(n_rows);
   k_synth_alpha<<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, gen, n_rows, heads, mix32(hash_key(seed, s1)), s1,
                                                      mix32(hash_key(seed, s2)), s2, out);
   GTA_LAUNCHED("k_synth_alpha");
@@ -6444,7 +6442,7 @@ int gta_synth_alpha(const int64_t* indptr, const int64_t* gen, int64_t n_rows, i
 int gta_row_ids(const int64_t* indptr, int64_t n_rows, int64_t nnz, int64_t* out, void* stream) {
   if (!indptr || n_rows < 0 || nnz < 0 || (nnz > 0 && !out)) return fail(GTA_ERR_ARG, "row_ids: bad arguments");
   if (n_rows == 0 || nnz == 0) return GTA_OK;
-  const dim3 grid(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock));
+  const dim3 grid = row_grid(n_rows);
   k_row_ids<<<grid, dim3(kBlock), 0, S(stream)>>>(indptr, n_rows, out);
   GTA_LAUNCHED("k_row_ids");
   return GTA_OK;

@@ -748,6 +748,7 @@ APPLY_EDGE_FLAT = True  # gta_apply_edge_flat where it applies (round 6); False:
 
 def _flat_aligned(Fo, a, lda, b, ldb, out, ldo):
     """The vector width of gta_apply_edge_flat (Fo / 64) divides every row start it reads or writes."""
+    # the same rule as vec_ok() in csrc/gta_kernels.hip, decided here before the call: keep the two alike
     vw = Fo // 64
 
     def ok(t, ld, width):
