@@ -16,14 +16,11 @@ import torch
 from gta_graph_tensor_acclelrator_for_general_gnn_amd import _lib, graph as G, ops
 from oracle import isa_ref
 
+from . import prep_ref
 from .test_gpu_footprint import CAP, Arena, _graph_in, _knobs, _ok, _p, _st
 from .test_gpu_ops import _check
 
 gpu = pytest.mark.gpu
-
-
-def _r16(b):
-    return (int(b) + 15) // 16 * 16
 
 
 def _merge_of(deg, B, row_edges):
@@ -56,66 +53,13 @@ def _csr_of(deg, n_cols, seed=0):
 
 def _decode(plan, n_rows):
     """(hdr, items [n_items, 3] = beg, row, len, row_ptr, row_items) of a device plan."""
-    raw = plan.buf.cpu().numpy()
-    hdr = raw[:128].view(np.int64)
-    B, mi, n_items, ri_off = int(hdr[0]), int(hdr[6]), int(hdr[4]), int(hdr[7])
-    assert int(hdr[2]) == n_rows and B == plan.blocks
-    # the layout of csrc/gta_kernels.hip (BlockedView): the fixed part ends where the items begin
-    off = 128 + _r16(n_rows * 4) + _r16(n_rows * (B + 1) * 4) + _r16(2 * 256 * 4) + _r16(256 * 4)
-    row_ptr = raw[off:off + (n_rows + 1) * 8].view(np.int64)
-    off += _r16((n_rows + 1) * 8) + _r16(n_rows * B * 4) + _r16(4097 * 8) + _r16(2 * 128 * 257 * 4)
-    assert off == ri_off - _r16(mi * 16), "plan layout: the item array does not follow the fixed part"
-    it = raw[off:off + n_items * 16].view(np.int32).reshape(n_items, 4)
-    beg = it[:, :2].copy().view(np.int64)[:, 0]
-    items = np.stack([beg, it[:, 2].astype(np.int64), it[:, 3].astype(np.int64)], axis=1)
-    row_items = raw[ri_off:ri_off + n_items * 4].view(np.int32).astype(np.int64)
-    return hdr, items, row_ptr, row_items
+    return prep_ref.decode_blocked(plan.buf, n_rows, plan.blocks)
 
 
 def _check_plan(plan, ip, ix, n_cols, blocks, item_edges, row_edges, class_major):
-    n = len(ip) - 1
-    deg = np.diff(ip)
-    bsize = -(-n_cols // blocks)
-    hdr, items, row_ptr, row_items = _decode(plan, n)
-    assert int(hdr[3]) == 0 and int(hdr[5]) == item_edges and int(hdr[8]) == row_edges and int(hdr[9]) == class_major
-    m_of = np.array([_merge_of(int(d), blocks, row_edges) for d in deg])
-    # items per row, by the rules (test_blocked_plan_items' formula)
-    want_rows = np.zeros(n, np.int64)
-    for r in range(n):
-        seg = np.bincount(ix[ip[r]:ip[r + 1]] // bsize, minlength=blocks)
-        seg = np.array([seg[j:j + m_of[r]].sum() for j in range(0, blocks, m_of[r])])
-        want_rows[r] = int(np.sum(-(-seg // item_edges)))
-    assert plan.n_items == int(hdr[4]) == int(want_rows.sum()) <= int(hdr[6])
-    assert np.array_equal(np.diff(row_ptr), want_rows) and row_ptr[0] == 0
-    beg, row, ln = items[:, 0], items[:, 1], items[:, 2]
-    if len(items) == 0:
-        return
-    # every edge in exactly one item, inside its row, inside one merged block of its row
-    assert (ln >= 1).all() and (ln <= item_edges).all() and (row >= 0).all() and (row < n).all()
-    assert (beg >= ip[row]).all() and (beg + ln <= ip[row + 1]).all()
-    cover = np.zeros(len(ix) + 1, np.int64)
-    np.add.at(cover, beg, 1)
-    np.add.at(cover, beg + ln, -1)
-    assert (np.cumsum(cover)[:len(ix)] == 1).all(), "an edge in no item, or in two"
-    m = m_of[row]
-    mb = ix[beg] // bsize // m
-    assert np.array_equal(mb, ix[beg + ln - 1] // bsize // m), "an item spans two merged blocks"
-    # ascending item id: the (class, merged block) key never decreases (not class-major: the first
-    # fine block of the merged block), and inside a key the capped lengths never increase
-    cls = np.log2(m).astype(np.int64) if class_major else np.zeros(len(m), np.int64)
-    key = cls * 64 + (mb if class_major else mb * m)
-    assert (np.diff(key) >= 0).all(), "item ids are not (class, merged block)-major"
-    same = np.diff(key) == 0
-    assert (np.diff(np.minimum(ln, 256))[same] <= 0).all(), "a group's items are not longest first"
-    # each row's list: its own items in (block, part) order -- columns are sorted, so edge order
-    assert sorted(row_items.tolist()) == list(range(len(items)))
-    lrow = np.repeat(np.arange(n), want_rows)
-    assert np.array_equal(row[row_items], lrow)
-    first = np.zeros(len(items), bool)
-    first[row_ptr[:-1][want_rows > 0]] = True
-    lb, ll = beg[row_items], ln[row_items]
-    assert np.array_equal(lb[first], ip[:-1][want_rows > 0])
-    assert np.array_equal(lb[1:][~first[1:]], (lb + ll)[:-1][~first[1:]]), "a row's list is not in (block, part) order"
+    """Every rule of the plan on the decoded device plan (tests/prep_ref.py, vectorised)."""
+    prep_ref.check_blocked(_decode(plan, len(ip) - 1), ip, ix, n_cols, blocks, item_edges, row_edges, class_major,
+                           n_items=plan.n_items)
 
 
 @gpu

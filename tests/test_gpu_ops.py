@@ -15,6 +15,8 @@ import torch
 from gta_graph_tensor_acclelrator_for_general_gnn_amd import graph as G, ops
 from oracle import isa_ref
 
+from . import prep_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -237,6 +239,8 @@ def test_plan_items_and_splits(dev):
     chunks = np.where(deg <= 256, 1, -(-deg // 256))
     assert p.n_items() == int(chunks.sum())
     assert p.n_split() == int((deg > 256).sum())
+    # the decoded item arrays and split table against the numpy restatement (tests/prep_ref.py)
+    prep_ref.check_row_plan(prep_ref.decode_row_plan(p.buf, g.n_rows, g.nnz, 256), ip, 256)
 
 
 @pytest.mark.parametrize("M,K,N", [(2449, 100, 128), (1000, 602, 128), (333, 37, 50)])
