@@ -29,7 +29,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import ir, ops
+from . import ir, ops, rewrites
 from .semantics import Semantics
 
 
@@ -144,6 +144,16 @@ def _forced(v):
     return v.force() if isinstance(v, Lazy) else v
 
 
+def _memo(cache, key, src, make):
+    """A per-run memo of a value derived from tensor src: the entry (src, its version, value) holds
+    src itself and hits only for that very object at the version it was stored at, so an address
+    (or an id) reused by another tensor never hits."""
+    ent = cache.get(key)
+    if ent is None or ent[0] is not src or ent[1] != src._version:
+        ent = cache[key] = (src, src._version, make())
+    return ent[2]
+
+
 REDUCERS = ("MAX", "MIN", "MEAN")  # gather COMP_TYPEs beside the sum (Executor._eval_reduce)
 
 
@@ -184,7 +194,7 @@ class Executor:
         self.sem = semantics or Semantics()
         self.plan_chunk = plan_chunk
         self.values = {}
-        self._nmm = {}  # node GEMMs of _node_mm in this run: (op, x) -> x W
+        self._nmm = {}  # node GEMMs of _node_mm in this run: (op, sf, id(table)) -> (table, its version, table W)
         self.alg_bytes = 0
         self.launches = 0
         # trace: per evaluated op, device time (HIP events), algorithmic bytes and launches, as
@@ -207,22 +217,19 @@ class Executor:
         #   ops.reduce_blocked (values identical to ops.reduce's: every output is one of its inputs);
         #   False keeps the row-chunked gta_reduce (A/B)
         self.reduce_blocked = True
-        self.consumers = {i: [] for i in range(len(opgraph))}
-        for i in range(len(opgraph)):
-            for src in opgraph.inputs[i]:
-                if src.kind == "op":
-                    self.consumers[src.op].append(i)
+        # the graph rewrites below are matched once, by rewrites.py (pure functions of the op graph)
+        self.consumers = cons = rewrites.consumers_of(opgraph)
         #   fuse_softmax: GAT's score -> SF -> per-row sum (-> divide) chain runs as one
         #   gta_edge_softmax launch (results equal to fp32 rounding, not bitwise)
         # column shards: per-row sums span ranks (unfused ops + exchanges); row shards own whole rows
         self.fuse_softmax = dist is None or dist.local_rows or dist.s.world == 1
-        self.softmax = self._match_softmax()
+        self.softmax = rewrites.softmax(opgraph, cons, self.sem)
         #   fuse_attention: the softmax chain's alpha (or v) * scatter_C(x) -> gather runs as one
         #   column-blocked gta_gat_aggregate_blocked (no [E, heads] tensor); attention_blocks
         #   None = ops.BlockedPlan.auto_blocks (used when >= 4), or a fixed block count
         self.fuse_attention = True
         self.attention_blocks = None
-        self.attn = self._match_attention()
+        self.attn = rewrites.attention(opgraph, cons, self.sem, self.softmax)
         self._att_state = {}
         #   softmax_shift: the chains' exp-form SFs run overflow-safe (SOFTMAX_SHIFT above); the row-max
         #   table of a chain is built once, on first use, and handed to both of its launches
@@ -249,10 +256,10 @@ class Executor:
         #   MM-then-aggregate (sum_e w_e x_src) W == sum_e w_e (x W)_src -- the layer's output
         #   to fp32 rounding, the gather's own value computed only if something asks for it
         self.mm_first = True
-        self.reorder = self._match_mm_first()
+        self.reorder = rewrites.mm_first(opgraph, cons)
         #   and through two hops (SGC: gather -> scatter C -> MUL -> gather -> MM): A (A x) W == A (A (x W)),
         #   both aggregates at the narrow width; the first gather's value computed only if asked for
-        self.two_hop = self._match_two_hop() if dist is None else {}
+        self.two_hop = rewrites.two_hop(opgraph, cons, self.reorder) if dist is None else {}
         #   node_mm: an applyedge MM of a scatter runs on the node tensor, (x W)[r(e)] == x[r(e)] W
         #   (bitwise: the same dot product per row), and stays a virtual scatter of x W
         #   mm_pushdown: MM(scatter a (+) scatter b) == (a W)[r(e)] (+) (b W)[r'(e)] (DGN op 2 -> 3),
@@ -262,20 +269,20 @@ class Executor:
         #   sibling_mm: applynode MMs that multiply the same node tensor run as ONE GEMM over the
         #   concatenated weights (x read once; e.g. GraphSAGE's x W3 and x W4, GAT's scores W1, W2)
         self.sibling_mm = True
-        self.pushdown = self._match_pushdown()
+        self.pushdown = rewrites.pushdown(opgraph, cons, self.sem)
         #   gather_acc: applynode ADD(gather G, node op T), each the other's only reader (GIN op 4:
         #   agg + (1+eps) x), runs as the aggregate accumulating into T's fresh output buffer:
         #   T + sum == sum + T bitwise, and the ADD pass over [N, F] disappears.  G and T stay
         #   available (recomputed on demand).
         self.gather_acc = dist is None or dist.local_rows or dist.s.world == 1
-        self.gacc = self._match_gather_acc()
+        self.gacc = rewrites.gather_acc(opgraph, cons, self.sem)
         self.gacc_t = {T: A for A, (_, _, T) in self.gacc.items()}  # node op T -> its ADD consumer
         #   edge_expr: a gather R whose edge value is a tree of applyedge ops (ADD / SUB / MUL / DIV,
         #   SF post-ops, a pushed-down MM), each read only by the next, runs as one
         #   gta_aggregate_expr: no [E, F] tensor for any op of the tree, bitwise the unfused ops and
         #   gather (DGN ops 2-8, PNA ops 5-8).  The tree's ops stay available, computed unfused if read.
         self.edge_expr = EDGE_EXPR
-        self.expr = self._match_edge_expr()
+        self.expr = rewrites.edge_expr(opgraph, cons, self.sem, self.softmax, self.attn, self.pushdown, self.gacc)
         self.expr_nodes = {i for e in self.expr.values() for i in e["nodes"]}
 
     # ---------------------------------------------------------------- inputs
@@ -320,6 +327,29 @@ class Executor:
     def _inputs(self, op):
         return [self._source(op, s) for s in range(len(self.g.inputs[op.idx]))]
 
+    def _pair(self, op, ins=None):
+        """op's evaluated operands (ins: those already at hand); an op with one graph input takes
+        `ext:<op>:1`, when given, as its second operand."""
+        ins = self._inputs(op) if ins is None else ins
+        extra = self._ext(op, 1) if len(self.g.inputs[op.idx]) == 1 else None
+        return ins if extra is None else ins + [self._wrap_ext(extra)]
+
+    def _pending(self, i):
+        """Op i's value is a Lazy nobody has forced: the op was fused away and is still unformed."""
+        raw = self.values.get(i)
+        return isinstance(raw, Lazy) and raw.v is None
+
+    @staticmethod
+    def _fp32(t):
+        return t if t.dtype == torch.float32 else t.float()  # exact widening of a bf16 table
+
+    @staticmethod
+    def _width(z):
+        """Feature width of an evaluated operand (0 for a fused producer not formed yet)."""
+        if isinstance(z, tuple):
+            return z[1].shape[1]
+        return z.t.shape[1] if not isinstance(z, Deferred) else 0
+
     # ---------------------------------------------------------- materialise
     def _edge_operand(self, v):
         """-> (tensor, mode, broadcast_row) usable by apply_edge / aggregate."""
@@ -328,7 +358,7 @@ class Executor:
         if isinstance(v, EdgeT):
             return v.t, "edge", False
         if isinstance(v, Scat):  # (a bf16 node table is widened: the element-wise kernels are fp32)
-            return (v.t if v.t.dtype == torch.float32 else v.t.float()), v.mode, False
+            return self._fp32(v.t), v.mode, False
         if isinstance(v, tuple) and v[0] == "row":
             return v[1], "edge", True
         raise TypeError(f"not an edge operand: {type(v).__name__}")
@@ -342,8 +372,7 @@ class Executor:
                 raise MemoryError(f"stream materialises a {nbytes / 2**30:.0f} GiB edge tensor (scatter not fused "
                                   "with its consumer); choose a fusion partition that keeps it virtual")
             self._count(self.graph.nnz * v.t.shape[1] * 4 * 2 + self.graph.nnz * 4)
-            t = v.t if v.t.dtype == torch.float32 else v.t.float()  # edge tensors are fp32 (exact widening)
-            return ops.scatter(self.graph, t, "C" if v.mode == "src" else "R")
+            return ops.scatter(self.graph, self._fp32(v.t), "C" if v.mode == "src" else "R")  # edge tensors are fp32
         if isinstance(v, Deferred):
             return self._materialize_deferred(v).t
         raise TypeError(type(v).__name__)
@@ -359,206 +388,11 @@ class Executor:
         self.launches += 1
 
     # ------------------------------------------------------- edge softmax
-    def _match_softmax(self):
-        """GAT edge-softmax chains keyed by their score op A (vTCAD/GraphOP/genGraphOP.py:51-60):
-            A = applyedge ADD(scatter R(a), scatter C(b));  V = applyedge SF(A);  G = gather R(V)
-          original (ops 6,7,8,10,9): D = applyedge V / scatter R(G)  -> alpha, one launch
-          trans    (ops 6,8,9):      V and G from one launch (V's other consumer aggregates it)"""
-        ops_, ins, cons = self.g.ops, self.g.inputs, self.consumers
-
-        def only(i):  # the single consumer of op i, or None
-            return cons[i][0] if len(cons[i]) == 1 else None
-
-        found = {}
-        for A in ops_:
-            if A.type != "applyedge" or A.comp != "ADD" or len(ins[A.idx]) != 2:
-                continue
-            srcs = [x.op for x in ins[A.idx] if x.kind == "op"]
-            if len(srcs) != 2:
-                continue
-            orders = sorted(ops_[i].order for i in srcs if ops_[i].type == "scatter")
-            if orders != ["C", "R"] or self.sem.bin_of(A) != "ADD":
-                continue
-            v = only(A.idx)
-            if v is None or ops_[v].type != "applyedge" or ops_[v].comp != "SF":
-                continue
-            gs = [c for c in cons[v] if ops_[c].type == "gather" and ops_[c].order == "R"]
-            if len(gs) != 1 or ops_[gs[0]].comp != "ADD":  # the chain's gather is the softmax SUM
-                continue
-            G = gs[0]
-            pat = {"A": A.idx, "V": v, "G": G, "D": None}
-            S = only(G)
-            if S is not None and ops_[S].type == "scatter" and ops_[S].order == "R":
-                D = only(S)
-                if D is not None and set(cons[v]) == {G, D} and ops_[D].type == "applyedge":
-                    dins = [x.op if x.kind == "op" else None for x in ins[D]]
-                    b = self.sem.bin_of(ops_[D])
-                    if (b == "DIV" and dins == [v, S]) or (b == "RDIV" and dins == [S, v]):
-                        pat["D"], pat["S"] = D, S
-            found[A.idx] = pat
-        return found
-
-    def _match_mm_first(self):
-        """{gather G: MM op M} for G -> M with M the only consumer, narrowing the width, and G
-        reading a scatter C directly or through a (weight) MUL (GraphSAGE / GCN layer 1)."""
-        found = {}
-        for G in self.g.ops:
-            if G.type != "gather" or G.order != "R" or G.comp != "ADD" or len(self.consumers[G.idx]) != 1:
-                continue  # (sum_e w x) W == sum_e w (x W) holds for the sum only
-            M = self.g.ops[self.consumers[G.idx][0]]
-            if M.type != "applynode" or M.comp != "MM" or len(self.g.inputs[M.idx]) != 1:
-                continue
-            if not (M.out_width and G.out_width and M.out_width < G.out_width):
-                continue
-            src = self.g.inputs[G.idx][0]
-            if src.kind != "op":
-                continue
-            P = self.g.ops[src.op]
-            if P.type == "applyedge" and P.comp == "MUL":
-                scat = [x.op for x in self.g.inputs[P.idx] if x.kind == "op" and self.g.ops[x.op].type == "scatter"]
-                if len(scat) != 1 or self.g.ops[scat[0]].order != "C":
-                    continue
-            elif not (P.type == "scatter" and P.order == "C"):
-                continue
-            found[G.idx] = M.idx
-        return found
-
-    def _match_two_hop(self):
-        """{first gather G1: second gather G2} for G1 -> scatter C -> [MUL by an edge weight] -> G2 with
-        G2 in reorder (its narrowing MM), each intermediate read only by the next op, and G1 of the
-        form mm_first takes (a scatter C of a node tensor, directly or through a weight MUL)."""
-        ops_, ins, cons = self.g.ops, self.g.inputs, self.consumers
-        found = {}
-        for G2 in self.reorder:
-            P = ops_[ins[G2][0].op]
-            if P.type == "scatter":
-                S = P
-            else:
-                sc = [x.op for x in ins[P.idx] if x.kind == "op" and ops_[x.op].type == "scatter"]
-                if len(sc) != 1 or cons[sc[0]] != [P.idx]:
-                    continue
-                S = ops_[sc[0]]
-            if S.order != "C" or not ins[S.idx] or ins[S.idx][0].kind != "op":
-                continue
-            G1 = ops_[ins[S.idx][0].op]
-            if G1.type != "gather" or G1.order != "R" or G1.comp != "ADD" or cons[G1.idx] != [S.idx]:
-                continue
-            src = ins[G1.idx][0]
-            if src.kind != "op":
-                continue
-            P1 = ops_[src.op]
-            if P1.type == "applyedge" and P1.comp == "MUL":
-                sc1 = [x.op for x in ins[P1.idx] if x.kind == "op" and ops_[x.op].type == "scatter"]
-                if len(sc1) != 1 or ops_[sc1[0]].order != "C":
-                    continue
-            elif not (P1.type == "scatter" and P1.order == "C"):
-                continue
-            found[G1.idx] = G2
-        return found
-
-    def _match_pushdown(self):
-        """{applyedge ADD of two scatters: its only consumer, a single-input applyedge MM}."""
-        found = {}
-        for op in self.g.ops:
-            if op.type != "applyedge" or op.comp != "ADD" or len(self.g.inputs[op.idx]) != 2:
-                continue
-            srcs = [x.op for x in self.g.inputs[op.idx] if x.kind == "op"]
-            if len(srcs) != 2 or any(self.g.ops[i].type != "scatter" for i in srcs):
-                continue
-            cons = self.consumers[op.idx]
-            if len(cons) != 1:
-                continue
-            m = self.g.ops[cons[0]]
-            if m.type == "applyedge" and m.comp == "MM" and len(self.g.inputs[m.idx]) == 1 \
-                    and self.sem.bin_of(op) == "ADD":
-                found[op.idx] = m.idx
-        return found
-
-    def _match_edge_expr(self):
-        """{gather G: plan} for a gather R (ADD) of an applyedge tree that gta_aggregate_expr's shapes
-        cover.  plan: shape, swap, bins, sfs, leaves ((op, slot) of a computed operand, or ("pmm", MM
-        op, k): the k-th scatter of a pushed-down MM's sum, multiplied on its node rows) and nodes (the
-        tree's ops, deferred until G runs).  Trees the existing fusions take are left to them: a lone
-        MUL / MM (the weighted aggregate), the attention chains, the GIN self-term gathers."""
-        ops_, ins, cons = self.g.ops, self.g.inputs, self.consumers
-        att = set(self.attn)
-        for pat in self.softmax.values():
-            att.update(i for i in (pat["A"], pat["V"], pat["D"]) if i is not None)
-        acc_g = {g for g, _, _ in self.gacc.values()}
-
-        def node(i):  # -> ("bin", bin, sf, left, right, ops) | ("leaf", ref) | None (not coverable)
-            o = ops_[i]
-            if o.type != "applyedge" or i in att:
-                return None
-            if o.comp == "SF":
-                if len(ins[i]) != 1 or ins[i][0].kind != "op" or cons[ins[i][0].op] != [i]:
-                    return None
-                c = node(ins[i][0].op)
-                if c is None or c[0] != "bin" or c[2] is not None or c[1] == "PMM":
-                    return None  # an SF on a pushed-down MM acts on the sum: not this tree
-                return ("bin", c[1], self.sem.sf_of(o), c[3], c[4], c[5] + [i])
-            if o.comp == "MM":
-                src = ins[i][0] if len(ins[i]) == 1 else None
-                if src is None or src.kind != "op" or self.pushdown.get(src.op) != i:
-                    return None
-                return ("bin", "PMM", None, ("leaf", ("pmm", i, 0)), ("leaf", ("pmm", i, 1)), [i])
-            if o.comp not in ("ADD", "SUB", "MUL", "DIV") or len(ins[i]) != 2:
-                return None
-            b = self.sem.bin_of(o)
-            kids = []
-            for slot, x in enumerate(ins[i]):
-                sub = None
-                if x.kind == "op" and cons[x.op] == [i] and ops_[x.op].type == "applyedge":
-                    sub = node(x.op)
-                kids.append(sub if sub is not None else ("leaf", (i, slot)))
-            if b == "RDIV":
-                b, kids = "DIV", kids[::-1]
-            if b not in ("ADD", "SUB", "MUL", "DIV"):
-                return None
-            return ("bin", b, None, kids[0], kids[1], [i])
-
-        def leafy(t):
-            return t[0] == "bin" and t[3][0] == "leaf" and t[4][0] == "leaf"
-
-        def b_of(t):
-            return "ADD" if t[1] == "PMM" else t[1]
-
-        found = {}
-        for G in ops_:
-            if G.type != "gather" or G.order != "R" or G.comp != "ADD" or G.idx in acc_g:
-                continue
-            src = ins[G.idx][0] if len(ins[G.idx]) == 1 else None
-            if src is None or src.kind != "op" or cons[src.op] != [G.idx]:
-                continue
-            t = node(src.op)
-            if t is None:
-                continue
-            L, R = t[3], t[4]
-            if leafy(t):
-                if t[1] in ("MUL", "PMM") and t[2] is None:
-                    continue  # the weighted aggregate / the pushed-down MM's own path
-                e = dict(shape=1, swap=False, bins=[b_of(t)], sfs=[t[2]], leaves=[L[1], R[1]], nodes=t[5])
-            elif leafy(L) and R[0] == "leaf":
-                e = dict(shape=2, swap=False, bins=[b_of(L), t[1]], sfs=[L[2], t[2]], leaves=[L[3][1], L[4][1], R[1]],
-                         nodes=L[5] + t[5])
-            elif L[0] == "leaf" and leafy(R):
-                e = dict(shape=2, swap=True, bins=[b_of(R), t[1]], sfs=[R[2], t[2]], leaves=[R[3][1], R[4][1], L[1]],
-                         nodes=R[5] + t[5])
-            elif leafy(L) and leafy(R):
-                e = dict(shape=3, swap=False, bins=[b_of(L), b_of(R), t[1]], sfs=[L[2], R[2], t[2]],
-                         leaves=[L[3][1], L[4][1], R[3][1], R[4][1]], nodes=L[5] + R[5] + t[5])
-            else:
-                continue
-            found[G.idx] = e
-        return found
-
     def _eval_edge_expr(self, G):
         """G's value from one gta_aggregate_expr launch, or None (then the tree runs unfused)."""
         e = self.expr[G.idx]
-        for i in e["nodes"]:
-            raw = self.values.get(i)
-            if not (isinstance(raw, Lazy) and raw.v is None):
-                return None
+        if not all(self._pending(i) for i in e["nodes"]):
+            return None
         operands, gathered = [], 0
         for ref in e["leaves"]:
             if ref[0] == "pmm":
@@ -570,7 +404,7 @@ class Executor:
             else:
                 v = self._source(self.g.ops[ref[0]], ref[1])
             if isinstance(v, Scat):
-                operands.append((v.t if v.t.dtype == torch.float32 else v.t.float(), v.mode))
+                operands.append((self._fp32(v.t), v.mode))
                 gathered += v.mode == "src"
             elif isinstance(v, EdgeT):
                 operands.append((v.t, "edge"))
@@ -591,44 +425,15 @@ class Executor:
             mop, add = self.g.ops[mm], self.g.inputs[mm][0].op
             self.values[mm] = Lazy(lambda mop=mop, add=add: self._pushdown_mm(mop, add))
         n, E = self.graph.n_rows, self.graph.nnz
-        self._count(E * (4 + 4 * F * gathered) + n * (8 + 4 * F))
+        self._count(self._gather_bytes(E, n, F, 4 * gathered))  # fp32 rows of every gathered operand
         return NodeT(self.dist.reduce_rows(y) if self.dist is not None else y)
-
-    def _match_gather_acc(self):
-        """{applynode ADD A: (gather G, slot of T, node op T)} for A = ADD(G, T) where A is G's and T's
-        only consumer, T a two-operand applynode ADD/MUL/DIV/SUB (so its output is a tensor it
-        allocated itself) and A carries no SF post-op."""
-        found = {}
-        for A in self.g.ops:
-            ins = self.g.inputs[A.idx]
-            if A.type != "applynode" or A.comp != "ADD" or len(ins) != 2 or any(x.kind != "op" for x in ins):
-                continue
-            if self.sem.bin_of(A) != "ADD":
-                continue
-            kinds = [self.g.ops[x.op].type for x in ins]
-            if sorted(kinds) != ["applynode", "gather"] or ins[0].op == ins[1].op:
-                continue
-            gs = 0 if kinds[0] == "gather" else 1
-            G, T = self.g.ops[ins[gs].op], self.g.ops[ins[1 - gs].op]
-            if G.order != "R" or G.comp != "ADD" or self.consumers[G.idx] != [A.idx] or self.consumers[T.idx] != [A.idx]:
-                continue
-            if T.comp not in ("ADD", "MUL") or len(self.g.inputs[T.idx]) != 2:
-                continue
-            cons = self.consumers[A.idx]
-            if len(cons) == 1 and self.g.ops[cons[0]].comp == "SF" and self.g.ops[cons[0]].type == "applynode":
-                continue  # keep A's SF post-op fusion
-            found[A.idx] = (G.idx, 1 - gs, T.idx)
-        return found
 
     def _self_term(self, top):
         """(x, s) when node op T = applynode MUL(x, s) of a node tensor x by a one-element scalar s
         (GIN op 3: (1 + eps) x): the aggregate can form T itself (gta_aggregate_self).  Else None."""
         if top.type != "applynode" or top.comp != "MUL" or self._binary(top) != "MUL":
             return None
-        ins = self._inputs(top)
-        if len(ins) == 1:
-            extra = self._ext(top, 1)
-            ins = ins + ([self._wrap_ext(extra)] if extra is not None else [])
+        ins = self._pair(top)
         if len(ins) != 2:
             return None
         xs = [z for z in ins if isinstance(z, NodeT)]
@@ -643,11 +448,9 @@ class Executor:
         aggregate forms it in its epilogue instead (no [N, F] T written and read back); only that
         form takes out_dtype bf16 (A stored rounded, for the fused MLP that reads it)."""
         G, slot_t, T = self.gacc[A.idx]
-        raw = self.values.get(G)
-        if not (isinstance(raw, Lazy) and raw.v is None):
+        if not self._pending(G):
             return None
-        tv = self.values.get(T)
-        if isinstance(tv, Lazy) and tv.v is None:
+        if self._pending(T):
             st = self._self_term(self.g.ops[T])
             y = self._eval_gather(self.g.ops[G], self_term=st, out_dtype=out_dtype) if st is not None else None
             if y is not None:
@@ -659,7 +462,7 @@ class Executor:
             return None
         y = self._eval_gather(self.g.ops[G], acc=t.t)
         if y.t.data_ptr() != t.t.data_ptr():  # G's form computed a fresh tensor: add it as the ADD would
-            raw.v = y
+            self.values[G].v = y
             return None
         top = self.g.ops[T]
         self.values[T] = Lazy(lambda: self._eval_applynode(top))  # T's buffer now holds A
@@ -669,16 +472,15 @@ class Executor:
         """applyedge MM of a virtual scatter: the GEMM runs over the node rows, the result stays virtual.
         The two scatters of one node table under one MM (DGN op 3's x[src] + x[dst]) share a GEMM."""
         W = self.tensors[f"w:{op.idx}"]
-        x, W = self._mm_dtypes(v.local, W)
-        if W.shape[0] != x.shape[1]:
-            raise ValueError(f"op {op.idx}: weight rows {W.shape[0]} != feature width {x.shape[1]}")
-        key = (op.idx, post_sf, x.data_ptr(), tuple(x.shape), tuple(x.stride()), x.dtype)
-        xw = self._nmm.get(key)
-        if xw is None:
-            xw = ops.update_mm(x, W, sf=post_sf)
-            self._count(x.shape[0] * (x.shape[1] * x.element_size() + W.shape[1] * 4) + W.numel() * W.element_size())
-            self._nmm[key] = xw
-        return Scat(xw, v.mode, v.fill)
+        if W.shape[0] != v.local.shape[1]:
+            raise ValueError(f"op {op.idx}: weight rows {W.shape[0]} != feature width {v.local.shape[1]}")
+
+        def gemm():
+            x, w = self._mm_dtypes(v.local, W)
+            self._count(x.shape[0] * (x.shape[1] * x.element_size() + w.shape[1] * 4) + w.numel() * w.element_size())
+            return ops.update_mm(x, w, sf=post_sf)
+        # keyed on the source table itself, before any widening: a temporary's address is no identity
+        return Scat(_memo(self._nmm, (op.idx, post_sf, id(v.local)), v.local, gemm), v.mode, v.fill)
 
     def _pushdown_mm(self, op, add_idx, post_sf=None):
         """MM(scatter a + scatter b) as (a W)[r_a(e)] + (b W)[r_b(e)]."""
@@ -758,10 +560,7 @@ class Executor:
             p = self.g.ops[v.op]
             if p.comp != "MUL" or self.sem.bin_of(p) != "MUL":
                 return None
-            pins = self._inputs(p)
-            if len(pins) == 1:
-                extra = self._ext(p, 1)
-                pins = pins + ([self._wrap_ext(extra)] if extra is not None else [])
+            pins = self._pair(p)
             xs = [z for z in pins if isinstance(z, Scat) and z.mode == "src"]
             ws = [z for z in pins if not (isinstance(z, Scat) and z.mode == "src")]
             if len(xs) != 1 or len(ws) > 1:
@@ -782,8 +581,7 @@ class Executor:
     def _eval_two_hop(self, G2, M):
         """M = A (A x) W as A (A (x W)): the first hop G1's value and its scatter stay unformed."""
         G1 = next((g1 for g1, g2 in self.two_hop.items() if g2 == G2.idx), None)
-        raw = self.values.get(G1) if G1 is not None else None
-        if not (self.mm_first and isinstance(raw, Lazy) and raw.v is None):
+        if not (self.mm_first and G1 is not None and self._pending(G1)):
             return None
         src = self.g.inputs[G2.idx][0]
         P = self.g.ops[src.op]
@@ -794,10 +592,7 @@ class Executor:
                 return None
             slots = [k for k, x in enumerate(self.g.inputs[P.idx])
                      if not (x.kind == "op" and self.g.ops[x.op].type == "scatter")]
-            others = [self._source(P, k) for k in slots]
-            if len(self.g.inputs[P.idx]) == 1:
-                extra = self._ext(P, 1)
-                others = [self._wrap_ext(extra)] if extra is not None else []
+            others = self._pair(P, [self._source(P, k) for k in slots])
             if len(others) > 1 or (others and isinstance(others[0], (tuple, Scat))):
                 return None
             if others:
@@ -816,7 +611,7 @@ class Executor:
         y = self._spmm(z, "src", w2)
         n, E, F = self.graph.n_rows, self.graph.nnz, xw.shape[1]
         for w in (w1, w2):
-            self._count(E * (4 + (4 if w is not None else 0) + 4 * F) + n * (8 + 4 * F))
+            self._count(self._gather_bytes(E, n, F, 4, heads=int(w is not None)))
         self.values[M.idx] = NodeT(y)
         return Lazy(lambda: self._gather_value(G2))
 
@@ -839,36 +634,9 @@ class Executor:
             xw = fill(xw)
         n, E, F = self.graph.n_rows, self.graph.nnz, xw.shape[1]
         y = self._spmm(xw, "src", w)
-        self._count(E * (4 + (4 if w is not None else 0) + 4 * F) + n * (8 + 4 * F))
+        self._count(self._gather_bytes(E, n, F, 4, heads=int(w is not None)))
         self.values[M.idx] = NodeT(self.dist.reduce_rows(y) if self.dist is not None else y)
         return Lazy(lambda: self._gather_value(G))
-
-    def _match_attention(self):
-        """{MUL op M: (softmax pattern, gather G2, x scatter S)} for M = scatter_C(x) * alpha (original,
-        alpha = the pattern's D) or * v (trans, v = V), whose only consumer is a gather R."""
-        found = {}
-        ops_, ins, cons = self.g.ops, self.g.inputs, self.consumers
-        for A, pat in self.softmax.items():
-            w_op = pat["D"] if pat["D"] is not None else pat["V"]
-            cands = [c for c in cons[w_op] if c != pat["G"]]
-            if len(cands) != 1:
-                continue
-            M = cands[0]
-            m = ops_[M]
-            if m.type != "applyedge" or m.comp != "MUL" or self.sem.bin_of(m) != "MUL" or len(ins[M]) != 2:
-                continue
-            srcs = [x.op if x.kind == "op" else None for x in ins[M]]
-            other = [o for o in srcs if o != w_op]
-            if len(other) != 1 or other[0] is None:
-                continue
-            S = other[0]
-            if ops_[S].type != "scatter" or ops_[S].order != "C":
-                continue
-            if len(cons[M]) != 1 or ops_[cons[M][0]].type != "gather" or ops_[cons[M][0]].order != "R" \
-                    or ops_[cons[M][0]].comp != "ADD":
-                continue
-            found[M] = (pat, cons[M][0], S)
-        return found
 
     def _eval_attention(self, G2, M, sf_out=None):
         """G2 = gather(scatter_C(x) * alpha|v) as one fused launch; None if the shapes do not allow it.
@@ -893,18 +661,17 @@ class Executor:
             return None
         norm = pat["D"] is not None
         G = pat["G"]
-        gv = self.values.get(G)
-        want = not norm and isinstance(gv, Lazy) and gv.v is None
+        want = not norm and self._pending(G)
         E, n = self.graph.nnz, self.graph.n_rows
         x = self._gather_cast(x)
         if shift is not None:
             y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
                                                 sf_out=sf_out, shift=shift.force())
-            self._count(E * (4 + xe * F + 4 * H) + n * (8 + 4 * F + 8 * H))
+            self._count(self._gather_bytes(E, n, F, xe, heads=H) + n * 8 * H)  # the scores' and the shift's rows
         else:
             y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
                                                 sf_out=sf_out)
-            self._count(E * (4 + xe * F + 4 * H) + n * (8 + 4 * F + 4 * H))
+            self._count(self._gather_bytes(E, n, F, xe, heads=H) + n * 4 * H)  # the scores' rows
         if want:
             self.values[G] = NodeT(sums)
         return NodeT(y)
@@ -954,38 +721,26 @@ class Executor:
 
     def _eval_applyedge(self, op, post_sf=None):
         E = self.graph.nnz
-        pushed = (op.comp == "MM" and self.mm_pushdown and self.g.inputs[op.idx]
-                  and self.g.inputs[op.idx][0].kind == "op"
-                  and self.pushdown.get(self.g.inputs[op.idx][0].op) == op.idx)
-        ins = [None] if pushed else self._inputs(op)
-        if pushed:
-            raw = self.values.get(self.g.inputs[op.idx][0].op)
-            if not (isinstance(raw, Lazy) and raw.v is None):
-                ins = self._inputs(op)
         if op.comp == "MM":
             src = self.g.inputs[op.idx][0]
-            raw = self.values.get(src.op) if src.kind == "op" else None
-            if self.mm_pushdown and src.kind == "op" and self.pushdown.get(src.op) == op.idx \
-                    and isinstance(raw, Lazy) and raw.v is None:
-                v = self._pushdown_mm(op, src.op, post_sf)
+            if self.mm_pushdown and src.kind == "op" and self.pushdown.get(src.op) == op.idx and self._pending(src.op):
+                v = self._pushdown_mm(op, src.op, post_sf)  # the sum is still unformed: go through it
                 if v is not None:
                     return v
-            if ins[0] is None:
-                ins = self._inputs(op)
+            ins = self._inputs(op)
             if self.node_mm and isinstance(ins[0], Scat):
                 return self._node_mm(op, ins[0], post_sf)
             return EdgeT(self._edge_mm(op, ins[0], post_sf))
+        ins = self._inputs(op)
         if op.comp == "SF":
             a, am, _ = self._edge_operand(ins[0])
             out = ops.apply_edge(self.graph, None, self.sem.sf_of(op), a, am)
             self._count(E * (a.shape[1] * 8))
             return EdgeT(out)
         bin_ = self._binary(op)
+        ins = self._pair(op, ins)
         if len(ins) == 1:  # unary ADD/MUL: identity unless an extra operand is supplied
-            extra = self._ext(op, 1)
-            ins = ins + ([self._wrap_ext(extra)] if extra is not None else [])
-            if len(ins) == 1:
-                return EdgeT(self._to_edge_tensor(ins[0]))
+            return EdgeT(self._to_edge_tensor(ins[0]))
         x, y = ins[0], ins[1]
         if bin_ == "RDIV":
             x, y, bin_ = y, x, "DIV"
@@ -1021,89 +776,127 @@ class Executor:
             x = x.float()
         return x, W
 
+    def _site(self, v, order):
+        """Where a gather of direction `order` reads evaluated operand v: (graph view, table, mode, n_out).
+        ORDER R walks the layer's CSR (n_rows outputs): a virtual scatter is read by index from its
+        node table in its own mode, anything else is formed as an edge tensor.  ORDER C (DIRECTION
+        src, template/ISA_defination.yaml:46-48) walks the stable CSC view (ops.CSC, gta_csc_build:
+        a column's edges in CSR order, no atomics; n_cols outputs), always in mode "src" of that
+        view: its "dst" rows for a scatter R, the column itself for a scatter C, the permutation
+        for an edge tensor.  The only place that knows these rules."""
+        if order == "C":
+            c = ops.csc(self.graph)
+            if isinstance(v, Scat):
+                return c.view("dst" if v.mode == "dst" else "src"), v.t, "src", self.graph.n_cols
+            return c.view("edge"), self._to_edge_tensor(v), "src", self.graph.n_cols
+        if isinstance(v, Scat):
+            return self.graph, v.t, v.mode, self.graph.n_rows
+        return self.graph, self._to_edge_tensor(v), "edge", self.graph.n_rows
+
+    @staticmethod
+    def _gather_bytes(E, n_out, F, row_es, heads=0, out_es=4, index=True):
+        """Algorithmic bytes of one aggregate-shaped launch: per edge an index (not in EDGE mode of
+        the CSR, index=False), `heads` fp32 weights and a row of F elements of row_es bytes; per
+        output row its two pointers and F elements of out_es bytes.  Each site passes the element
+        sizes it has always charged (DESIGN.md §1.1 lists where they disagree)."""
+        return E * ((4 if index else 0) + 4 * heads + row_es * F) + n_out * (8 + out_es * F)
+
     def _eval_gather(self, op, acc=None, self_term=None, out_dtype=torch.float32):
-        """self_term (x, s): y = x * s + the aggregate, or None if this gather's form cannot take it;
+        """The ISA gather, both DIRECTIONs (_site).  A fused producer stays virtual: a scatter operand
+        is gathered by index, a MUL by an edge weight runs as one weighted aggregate, ORDER R takes an
+        MM on the node side; anything else is materialised as an edge tensor and summed.
+        self_term (x, s): y = x * s + the aggregate, or None if this gather's form cannot take it;
         out_dtype (self_term only): y's storage dtype."""
         if op.comp in REDUCERS:  # COMP_TYPE MAX / MIN / MEAN: no accumulate, no self term, none of the sum's fusions
             return None if (acc is not None or self_term is not None) else self._eval_reduce(op)
-        if op.order == "C":
-            if acc is not None or self_term is not None:
-                return None
-            return self._eval_gather_c(op)
+        if op.order == "C" and (acc is not None or self_term is not None):
+            return None  # ORDER C takes no accumulator and no self term
         src = self.g.inputs[op.idx][0]
+        E = self.graph.nnz
         if self_term is not None:
             v = self._source(op, 0) if not (self.fuse_attention and src.kind == "op" and src.op in self.attn) else None
             if isinstance(v, Deferred):
                 p = self.g.ops[v.op]
-                pins = self._inputs(p)
-                if p.comp == "MM" or self._binary(p) != "MUL":
-                    return None
-                if len(pins) == 1:
-                    extra = self._ext(p, 1)
-                    pins = pins + ([self._wrap_ext(extra)] if extra is not None else [])
-                if len(pins) != 2:
+                pins = self._pair(p)
+                if p.comp == "MM" or self._binary(p) != "MUL" or len(pins) != 2:
                     return None
                 y = self._weighted_aggregate(pins[0], pins[1], self_term=self_term, out_dtype=out_dtype)
                 return None if y is None else NodeT(y)
             if isinstance(v, Scat):
                 y = self._spmm(v.t, v.mode, None, self_term=self_term, out_dtype=out_dtype)
                 if y is not None:
-                    n, E = self.graph.n_rows, self.graph.nnz
-                    self._count(E * (4 + v.t.shape[1] * v.t.element_size()) + n * (8 + v.t.shape[1] * y.element_size()))
+                    self._count(self._gather_bytes(E, self.graph.n_rows, v.t.shape[1], v.t.element_size(),
+                                                   out_es=y.element_size()))
                     return NodeT(y)
             return None
-        if self.fuse_attention and src.kind == "op" and src.op in self.attn:
+        if self.fuse_attention and src.kind == "op" and src.op in self.attn:  # (its gather is ORDER R: rewrites.attention)
             raw = self.values.get(src.op)
             if isinstance(raw, (Deferred, Lazy)):
                 y = self._eval_attention(op, src.op)
                 if y is not None:
                     return y
         v = self._source(op, 0)
-        n, E = self.graph.n_rows, self.graph.nnz
         if isinstance(v, Deferred):
             p = self.g.ops[v.op]
-            pins = self._inputs(p)
             if p.comp == "MM":
-                if self.node_mm and isinstance(pins[0], Scat):  # gather(x[r(e)] W) = SpMM of x W
-                    sw = self._node_mm(p, pins[0])
-                    y = self._spmm(sw.t, sw.mode, None)
-                    self._count(E * (4 + sw.t.shape[1] * 4) + n * (8 + sw.t.shape[1] * 4))
-                    return NodeT(y)
-                xe = self._edge_mm(p, pins[0])
-                y = ops.gather_add(self.graph, xe)
-                self._count(E * xe.shape[1] * 4 + n * xe.shape[1] * 4)
-                return NodeT(y)
-            bin_ = self._binary(p)
-            if len(pins) == 1:
-                extra = self._ext(p, 1)
-                pins = pins + ([self._wrap_ext(extra)] if extra is not None else [])
-            if len(pins) == 1:
-                v = pins[0]
-            elif bin_ == "MUL":
-                return NodeT(self._weighted_aggregate(pins[0], pins[1], acc))
-            else:  # a non-MUL fused pair: evaluate the producer, then gather
+                if op.order == "R":  # (ORDER C has no node-side form: it sums the formed product)
+                    return NodeT(self._gather_mm(p))
+            else:
+                pins = self._pair(p)
+                if len(pins) == 1 and op.order == "R":
+                    v = pins[0]  # an identity ADD / MUL: ORDER R gathers its operand as it is, ORDER C forms it
+                elif len(pins) == 2 and self._binary(p) == "MUL":
+                    y = self._weighted_aggregate(pins[0], pins[1], acc, order=op.order)
+                    if y is not None:
+                        return NodeT(y)
+            if isinstance(v, Deferred):  # any other fused pair: evaluate the producer, then gather
                 v = self._materialize_deferred(v)
-        if isinstance(v, Scat):
-            y = self._spmm(v.t, v.mode, None, acc)
-            self._count(E * (4 + v.t.shape[1] * 4) + n * (8 + v.t.shape[1] * 4))
-            return NodeT(y)
-        xe = self._to_edge_tensor(v)
-        y = ops.aggregate(self.graph, xe, "edge", None, out=acc, accumulate=acc is not None, plan=self._plan())
-        self._count(E * xe.shape[1] * 4 + n * (8 + xe.shape[1] * 4))
+        scat = isinstance(v, Scat)
+        g, t, mode, n_out = self._site(v, op.order)
+        F = t.shape[1]
+        if op.order == "C":
+            # column-blocked like direction R when the table is large, but only for a scatter R over
+            # the "dst" view (the transposed aggregate); the byte model charges the table's own rows
+            if scat and v.mode == "dst":
+                y = self._spmm(t, "src", None, graph=g)
+            else:
+                y = ops.aggregate(g, t, "src", None, plan=self._plan())
+            self._count(self._gather_bytes(E, n_out, F, t.element_size() if scat else 4))
+        elif scat:
+            y = self._spmm(t, mode, None, acc)
+            self._count(self._gather_bytes(E, n_out, F, 4))
+        else:
+            y = ops.aggregate(g, t, "edge", None, out=acc, accumulate=acc is not None, plan=self._plan())
+            self._count(self._gather_bytes(E, n_out, F, 4, index=False))
         return NodeT(y)
+
+    def _gather_mm(self, p):
+        """ORDER R gather of a fused applyedge MM p: gather(x[r(e)] W) = SpMM of x W on the node side,
+        else the edge GEMM and a plain segment sum."""
+        n, E = self.graph.n_rows, self.graph.nnz
+        pins = self._inputs(p)
+        if self.node_mm and isinstance(pins[0], Scat):
+            sw = self._node_mm(p, pins[0])
+            y = self._spmm(sw.t, sw.mode, None)
+            self._count(self._gather_bytes(E, n, sw.t.shape[1], 4))
+            return y
+        xe = self._edge_mm(p, pins[0])
+        y = ops.gather_add(self.graph, xe)
+        self._count(E * xe.shape[1] * 4 + n * xe.shape[1] * 4)
+        return y
 
     def _plan(self):
         return self.plan_chunk if self.plan_chunk else None
 
     def _eval_reduce(self, op):
         """The ISA gather whose COMP_TYPE is MAX, MIN or MEAN (include/gta.h gta_reduce; the sum's
-        COMP_TYPE is ADD), both DIRECTIONs.  A virtual scatter is reduced by index straight from the
+        COMP_TYPE is ADD), both DIRECTIONs (_site).  A virtual scatter is reduced by index straight from the
         node table (fp32 or bf16; no [E, F] tensor); everything else -- an edge tensor, or a fused
         applyedge MUL / MM producer, which is first formed as the unfused op forms it -- in EDGE
         mode.  MAX / MIN run gta_reduce; MEAN is the plain ADD aggregate with row_scale = 1 / deg
-        (empty rows 0).  ORDER C runs the same kernels over the graph's CSC views, the degree then
-        the out-degree from colptr.  None of the rewrites that rely on the gather being a sum applies
-        (mm_first, two_hop, gather_acc, the weighted aggregate, the attention chains, edge_expr)."""
+        (empty rows 0; ORDER C: the out-degree from colptr).  None of the rewrites that rely on the
+        gather being a sum applies (mm_first, two_hop, gather_acc, the weighted aggregate, the
+        attention chains, edge_expr)."""
         d = self.dist
         if d is not None and d.s.world > 1 and (not d.local_rows or op.order == "C"):
             raise NotImplementedError(
@@ -1112,38 +905,26 @@ class Executor:
         v = self._source(op, 0)
         if isinstance(v, Deferred):
             v = self._materialize_deferred(v)
-        E, F4 = self.graph.nnz, 4
-        if op.order == "C":
-            c = ops.csc(self.graph)
-            n_out = self.graph.n_cols
-            if isinstance(v, Scat):
-                t, g, mode = v.t, c.view("dst" if v.mode == "dst" else "src"), "src"
-            else:
-                t, g, mode = self._to_edge_tensor(v), c.view("edge"), "src"
-            nbytes = E * (4 + t.shape[1] * t.element_size()) + n_out * (8 + t.shape[1] * F4)
-        else:
-            n_out = self.graph.n_rows
-            if isinstance(v, Scat):
-                t, g, mode = v.t, self.graph, v.mode
-                nbytes = E * (4 + t.shape[1] * F4) + n_out * (8 + t.shape[1] * F4)
-            else:
-                t, g, mode = self._to_edge_tensor(v), self.graph, "edge"
-                nbytes = E * t.shape[1] * F4 + n_out * (8 + t.shape[1] * F4)
+        scat, col = isinstance(v, Scat), op.order == "C"
+        g, t, mode, n_out = self._site(v, op.order)
+        E, F = self.graph.nnz, t.shape[1]
+        # (ORDER C charges the table's own element size, ORDER R 4 bytes; EDGE mode of the CSR reads no index)
+        nbytes = self._gather_bytes(E, n_out, F, t.element_size() if col else 4, index=col or scat)
         # column-blocked when a source-gathered node table outgrows L2 (_spmm's gate, evaluated before
         # any blocked op is named): ORDER R of a scatter C on the layer's CSR, ORDER C of a scatter R
         # over the transposed view.  MAX / MIN values are identical by construction; MEAN moves only
-        # under gather_dtype bf16 (its blocked sum order would change the default bits)
-        B, view = 0, None
-        if self.reduce_blocked and isinstance(v, Scat):
+        # under gather_dtype bf16 (its blocked sum order would change the default bits), and never in
+        # ORDER C (the views are not cast)
+        B = 0
+        if self.reduce_blocked and scat:
             on = self.gather_dtype == torch.bfloat16
-            if op.order != "C" and v.mode == "src" and (op.comp != "MEAN" or on):
+            if not col and v.mode == "src" and (op.comp != "MEAN" or on):
                 B = self._blocked_blocks(t, "src", 0)
-            elif op.order == "C" and v.mode == "dst" and op.comp != "MEAN":
-                view = g
-                B = self._blocked_blocks(t, "src", 0, view)
+            elif col and v.mode == "dst" and op.comp != "MEAN":
+                B = self._blocked_blocks(t, "src", 0, g)
         if B:
-            tb = self._gather_cast(t) if view is None else t
-            nbytes = E * (4 + t.shape[1] * tb.element_size()) + n_out * (8 + t.shape[1] * F4)
+            tb = t if col else self._gather_cast(t)
+            nbytes = self._gather_bytes(E, n_out, F, tb.element_size())
             if op.comp == "MEAN":
                 y = ops.aggregate_blocked(g, tb, None, row_scale=_mean_scale(g), blocks=B)
             else:
@@ -1155,105 +936,44 @@ class Executor:
         self._count(nbytes)
         return NodeT(y)
 
-    def _eval_gather_c(self, op):
-        """ISA gather with DIRECTION src (ORDER C, template/ISA_defination.yaml:46-48): y[j] = sum of
-        the edge value over the edges whose SOURCE is j, y [n_cols, F].  Runs the ordered row kernels
-        over the graph's stable CSC view (ops.CSC, gta_csc_build): a column's edges are summed in CSR
-        order, deterministic, no atomics.  A fused producer stays virtual as in direction R: a scatter
-        operand is gathered by index (its CSC view: "dst" rows for scatter R, the column itself for
-        scatter C), a MUL by an edge weight runs as one weighted aggregate (the weight read in CSC
-        order through one permuting copy); anything else is materialised as an edge tensor and summed
-        by CSC position (gta_gather_add's direction C)."""
-        c = ops.csc(self.graph)
-        E, nc = self.graph.nnz, self.graph.n_cols
-        v = self._source(op, 0)
-        if isinstance(v, Deferred):
-            p = self.g.ops[v.op]
-            if p.comp != "MM" and self._binary(p) == "MUL":
-                pins = self._inputs(p)
-                if len(pins) == 1:
-                    extra = self._ext(p, 1)
-                    pins = pins + ([self._wrap_ext(extra)] if extra is not None else [])
-                if len(pins) == 2:
-                    y = self._weighted_c(c, pins[0], pins[1])
-                    if y is not None:
-                        return NodeT(y)
-            v = self._materialize_deferred(v)
-        if isinstance(v, Scat):
-            if v.mode == "dst":  # the transposed aggregate: column-blocked like direction R when the table is large
-                y = self._spmm(v.t, "src", None, graph=c.view("dst"))
-            else:
-                y = ops.aggregate(c.view("src"), v.t, "src", None, plan=self._plan())
-            self._count(E * (4 + v.t.shape[1] * v.t.element_size()) + nc * (8 + v.t.shape[1] * 4))
-            return NodeT(y)
-        xe = self._to_edge_tensor(v)
-        y = ops.aggregate(c.view("edge"), xe, "src", None, plan=self._plan())
-        self._count(E * (4 + xe.shape[1] * 4) + nc * (8 + xe.shape[1] * 4))
-        return NodeT(y)
-
-    def _weighted_c(self, c, u, v):
-        """sum over a source column's edges of u(e) (.) v(e) (direction C form of _weighted_aggregate):
-        the narrower operand is the (head) weight, permuted once into CSC order; None when neither
-        operand is an edge/scatter tensor of a width the aggregate takes."""
-        def width(z):
-            if isinstance(z, tuple):
-                return z[1].shape[1]
-            return z.t.shape[1] if not isinstance(z, Deferred) else 0
-
-        x, w = (u, v) if width(u) >= width(v) else (v, u)
-        if isinstance(x, tuple) or isinstance(x, Deferred) or isinstance(w, Deferred):
+    def _weighted_aggregate(self, u, v, acc=None, self_term=None, out_dtype=torch.float32, order="R"):
+        """sum_e u(e) (.) v(e) over each output node's edges (_site): the wider operand is the feature
+        row, the narrower the (head) weight.  self_term: see _eval_gather (None back if this form
+        cannot take it).  ORDER C reads the weight in CSC order through one permuting copy, and
+        gives None back (the caller then forms the product) where ORDER R forms an operand or raises."""
+        E, col = self.graph.nnz, order == "C"
+        x, w = (u, v) if self._width(u) >= self._width(v) else (v, u)
+        if col and (isinstance(x, (tuple, Deferred)) or isinstance(w, Deferred)):
             return None
-        E, nc = self.graph.nnz, self.graph.n_cols
-        if isinstance(w, tuple) and w[0] == "row":  # a constant row weight: aggregate then scale (linear)
-            if isinstance(x, Scat):
-                y = ops.aggregate(c.view("dst" if x.mode == "dst" else "src"), x.t, "src", None, plan=self._plan())
-            else:
-                y = ops.aggregate(c.view("edge"), self._to_edge_tensor(x), "src", None, plan=self._plan())
-            self._count(E * (4 + 4 * y.shape[1]) + nc * (8 + 4 * y.shape[1]))
-            return ops.apply_node("MUL", None, y, w[1], b_broadcast_row=True)
-        wt = self._to_edge_tensor(w)
-        if wt.dtype != torch.float32 or width(x) % wt.shape[1]:
-            return None
-        wc = ops.apply_edge(c.view("edge"), None, None, wt, "src")  # wc[k] = wt[perm[k]]: CSC order
-        if isinstance(x, Scat):
-            view, table = c.view("dst" if x.mode == "dst" else "src"), x.t
-        else:
-            view, table = c.view("edge"), self._to_edge_tensor(x)
-        if isinstance(x, Scat) and x.mode == "dst":  # column-blocked like direction R when the table is large
-            y = self._spmm(table, "src", wc, graph=view)
-        else:
-            y = ops.aggregate(view, table, "src", wc, plan=self._plan())
-        F, H = table.shape[1], wc.shape[1]
-        self._count(E * 8 * H + E * (4 + 4 * H + table.element_size() * F) + nc * (8 + 4 * F))
-        return y
-
-    def _weighted_aggregate(self, u, v, acc=None, self_term=None, out_dtype=torch.float32):
-        """sum_e u(e) (.) v(e): the wider operand is the feature row, the narrower the (head) weight.
-        self_term: see _eval_gather (None back if this form cannot take it)."""
-        n, E = self.graph.n_rows, self.graph.nnz
-
-        def width(z):
-            if isinstance(z, tuple):
-                return z[1].shape[1]
-            return z.t.shape[1] if not isinstance(z, Deferred) else 0
-
-        x, w = (u, v) if width(u) >= width(v) else (v, u)
         if isinstance(w, tuple) and w[0] == "row":  # constant row weight: aggregate then scale (linear)
             if self_term is not None:
                 return None
-            y = self._unweighted(x)
+            g, xt, mode, n_out = self._site(x, order)
+            y = ops.aggregate(g, xt, mode, None, plan=self._plan())
+            if col:  # (ORDER R has never charged this aggregate: DESIGN.md §1.1)
+                self._count(self._gather_bytes(E, n_out, y.shape[1], 4))
             return ops.apply_node("MUL", None, y, w[1], b_broadcast_row=True)
         wt = self._to_edge_tensor(w)
-        if isinstance(x, Scat):
-            xt, mode = x.t, x.mode
-        else:
-            xt, mode = self._to_edge_tensor(x), "edge"
-        if xt.shape[1] % wt.shape[1]:
-            raise ValueError(f"weighted aggregate: weight width {wt.shape[1]} does not divide {xt.shape[1]}")
+        if col:
+            if wt.dtype != torch.float32 or self._width(x) % wt.shape[1]:
+                return None
+            wt = ops.apply_edge(ops.csc(self.graph).view("edge"), None, None, wt, "src")  # wt[perm[k]]: CSC order, once
+        g, xt, mode, n_out = self._site(x, order)
+        F, H = xt.shape[1], wt.shape[1]
+        if col:
+            # column-blocked like direction R when the table is large, but only for a scatter R over the "dst" view
+            if isinstance(x, Scat) and x.mode == "dst":
+                y = self._spmm(xt, "src", wt, graph=g)
+            else:
+                y = ops.aggregate(g, xt, "src", wt, plan=self._plan())
+            self._count(E * 8 * H + self._gather_bytes(E, n_out, F, xt.element_size(), heads=H))  # the permuting copy too
+            return y
+        if F % H:
+            raise ValueError(f"weighted aggregate: weight width {H} does not divide {F}")
         y = self._spmm(xt, mode, wt, acc, self_term, out_dtype)
         if y is None:
             return None
-        self._count(E * (4 + 4 * wt.shape[1] + xt.element_size() * xt.shape[1]) + n * (8 + y.element_size() * xt.shape[1]))
+        self._count(self._gather_bytes(E, n_out, F, xt.element_size(), heads=H, out_es=y.element_size()))
         return y
 
     def _spmm(self, xt, mode, wt, acc=None, self_term=None, out_dtype=torch.float32, graph=None):
@@ -1302,23 +1022,14 @@ class Executor:
     def _gather_cast(self, t):
         """The node table t as the blocked kernels gather it under gather_dtype: t itself (no option,
         or t already of that type), else its RNE rounding to bf16 -- made once per table value and
-        shared by its consumers.  The cache entry holds t itself and is used only for that very
-        tensor at the version it was cast at, so an address reused by another tensor never hits."""
+        shared by its consumers (_memo: identity and version checked)."""
         if self.gather_dtype != torch.bfloat16 or t.dtype != torch.float32:
             return t
-        ent = self._gather_cache.get(id(t))
-        if ent is not None and ent[0] is t and ent[1] == t._version:
-            return ent[2]
-        tb = ops.pitched(t.to(torch.bfloat16))
-        self._count(t.shape[0] * t.shape[1] * 6)
-        self.gather_casts += 1
-        self._gather_cache[id(t)] = (t, t._version, tb)
-        return tb
-
-    def _unweighted(self, x):
-        if isinstance(x, Scat):
-            return ops.aggregate(self.graph, x.t, x.mode, None, plan=self._plan())
-        return ops.aggregate(self.graph, self._to_edge_tensor(x), "edge", None, plan=self._plan())
+        def cast():
+            self._count(t.shape[0] * t.shape[1] * 6)
+            self.gather_casts += 1
+            return ops.pitched(t.to(torch.bfloat16))
+        return _memo(self._gather_cache, id(t), t, cast)
 
     def _eval_applynode(self, op, post_sf=None):
         if self.gather_acc and post_sf is None and op.idx in self.gacc:
@@ -1338,11 +1049,9 @@ class Executor:
             self._count(n * a.shape[1] * 8)
             return NodeT(y)
         bin_ = self._binary(op)
+        ins = self._pair(op, ins)
         if len(ins) == 1:
-            extra = self._ext(op, 1)
-            if extra is None:
-                return NodeT(self._node(ins[0]))
-            ins = ins + [self._wrap_ext(extra)]
+            return NodeT(self._node(ins[0]))
         x, y = ins[0], ins[1]
         if bin_ == "RDIV":
             x, y, bin_ = y, x, "DIV"
@@ -1369,8 +1078,8 @@ class Executor:
         fused_into = {p: c for p, c, _ in block.fused}
         if op.type == "scatter":
             src = self.g.inputs[op.idx][0]
-            raw = self.values.get(src.op) if src.kind == "op" else None
-            if isinstance(raw, Lazy) and raw.v is None:  # keep a fused-away producer unforced
+            if src.kind == "op" and self._pending(src.op):  # keep a fused-away producer unforced
+                raw = self.values[src.op]
                 return Lazy(lambda: (raw.force(), self._eval(op, block))[1])
             v = self._source(op, 0)
             if isinstance(v, tuple):
@@ -1511,8 +1220,7 @@ class Executor:
         x = None
         src = self.g.inputs[a.idx][0]
         if self.mlp_bf16_sum and self.gather_acc and src.kind == "op" and src.op in self.gacc:
-            raw = self.values.get(src.op)
-            if isinstance(raw, Lazy) and raw.v is None:
+            if self._pending(src.op):
                 y = self._eval_gather_acc(self.g.ops[src.op], out_dtype=torch.bfloat16)
                 if y is not None and ops.update_mlp_supported(y.t, w1, w2):
                     x = y.t

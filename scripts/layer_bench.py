@@ -79,7 +79,9 @@ def main(names=None, reps=5, trace=False, graphed=False, gather_dtype=None):
 if __name__ == "__main__":
     from gta_graph_tensor_acclelrator_for_general_gnn_amd import ops
     argv = [a for a in sys.argv[1:] if a not in ("--trace", "--hipgraph", "--no-mlp", "--graph-all", "--no-bf16-sum",
-                                                 "--no-edge-flat", "--no-edge-expr", "--stable-softmax")]
+                                                 "--no-edge-flat", "--no-edge-expr", "--stable-softmax", "--no-auto-graph")]
+    if "--no-auto-graph" in sys.argv[1:]:  # every forward through the executor itself (its host time included), no replay
+        executor.set_auto_graph(False)
     if "--stable-softmax" in sys.argv[1:]:  # the GAT softmax chains shifted by their row maxima (A/B of the shift pass)
         executor.SOFTMAX_SHIFT = True
     if "--no-edge-expr" in sys.argv[1:]:  # the applyedge trees of DGN / PNA unfused (A/B of gta_aggregate_expr, ABI 14)

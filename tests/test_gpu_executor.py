@@ -17,7 +17,7 @@ from oracle.exec_ref import execute_ref
 from oracle.sampled import SampledChecker
 
 from .conftest import load_manifest
-from .test_ir_executor_cpu import compare
+from .test_ir_executor_cpu import compare, pushdown_executor
 
 pytestmark = pytest.mark.gpu
 
@@ -529,3 +529,20 @@ def test_transposed_spmm_column_blocked(cora, dev, H):
         torch.cuda.synchronize()
         err = np.abs(y.cpu().numpy() - ref)
         assert (err <= 1e-5 * mag + 1e-6).all(), (blocked, float(err.max()))
+
+
+def test_pushed_down_mm_of_two_bf16_tables_on_gpu(dev):
+    """MM(scatter R(a) + scatter C(b)) with two distinct bf16 tables and an fp32 W: _pushdown_mm's edge
+    tensor is bitwise (a W)[dst] + (b W)[src] from the same kernels -- the widened temporaries of a
+    and b may share an address, the run's GEMM memo must not take one for the other."""
+    g = G.synthetic(64, 256, device=dev)
+    gen = torch.Generator().manual_seed(13)
+    a, b = (torch.randn(64, 32, generator=gen).to(torch.bfloat16).to(dev) for _ in range(2))
+    W = torch.randn(32, 16, generator=gen).to(dev)
+    ex = pushdown_executor(g, a, b, W)
+    got = ex._pushdown_mm(ex.g.ops[3], 2).t
+    want = ops.apply_edge(g, "ADD", None,
+                          ops.update_mm(a.float(), W), "dst",
+                          ops.update_mm(b.float(), W), "src")
+    torch.cuda.synchronize()
+    assert got.shape == (g.nnz, 16) and torch.equal(got, want)

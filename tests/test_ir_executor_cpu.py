@@ -255,6 +255,58 @@ def test_gather_acc_fusion_cpu(golden_dir, manifest, monkeypatch):
         assert nbytes[True] < nbytes[False]
 
 
+def pushdown_executor(g, a, b, W):
+    """DGN ops 0-3 alone -- scatter R(a), scatter C(b), their ADD, its MM by W -- in an executor whose
+    two scatters are already virtual: what _pushdown_mm(ops[3], 2) multiplies on the node rows."""
+    from gta_graph_tensor_acclelrator_for_general_gnn_amd import frontend
+    recs = frontend.gen_ops("DGN", 1, g.n_rows, g.nnz, a.shape[1], False)[:4]
+    assert [(r["TYPE"], r["COMP_TYPE"]) for r in recs] == [("scatter", "NONE"), ("scatter", "NONE"),
+                                                           ("applyedge", "ADD"), ("applyedge", "MM")]
+    recs = [dict(r, OUTPUT=dict(r["OUTPUT"])) for r in recs]
+    recs[0]["ORDER"], recs[1]["ORDER"], recs[3]["OUTPUT"]["output_list"] = "R", "C", []
+    recs[3]["OUTPUT"]["size_per_feature"] = 4 * W.shape[1]
+    ex = executor.Executor(ir.OpGraph(recs), None, g, {"w:3": W}, Semantics.for_network("DGN", False))
+    assert ex.pushdown == {2: 3}
+    ex.values[0], ex.values[1] = executor.Scat(a, "dst"), executor.Scat(b, "src")
+    return ex
+
+
+def test_pushed_down_mm_never_aliases_two_tables_at_one_address(monkeypatch):
+    """Two distinct bf16 tables under one pushed-down MM with an fp32 W are widened into temporaries
+    that an allocator hands the same address: made certain here by a _mm_dtypes stand-in that widens
+    into one buffer, so both present the same data_ptr, shape, stride and dtype.  Each must still be
+    multiplied itself (a W and b W); the same table read by both scatters is multiplied once."""
+    from oracle import isa_ref
+    monkeypatch.setattr(executor, "ops", fake_ops)
+    g = G.synthetic(40, 200, seed=2)
+    gen = torch.Generator().manual_seed(9)
+    a, b = (torch.randn(40, 16, generator=gen).to(torch.bfloat16) for _ in range(2))
+    W = torch.randn(16, 8, generator=gen)
+    buf = torch.empty(40, 16)
+
+    def one_buffer(x, w):
+        assert w.dtype == torch.float32 and x.dtype == torch.bfloat16
+        return buf.copy_(x), w
+    monkeypatch.setattr(executor.Executor, "_mm_dtypes", staticmethod(one_buffer))
+    gemms = []
+    monkeypatch.setattr(fake_ops, "update_mm", lambda *p, _real=fake_ops.update_mm, **k: gemms.append(1) or _real(*p, **k))
+    ex = pushdown_executor(g, a, b, W)
+    mm = ex.g.ops[3]
+    aw, bw = ex._node_mm(mm, ex.values[0]), ex._node_mm(mm, ex.values[1])
+    want = [isa_ref.mm(t.double().numpy(), W.double().numpy(), None, None).astype(np.float32) for t in (a, b)]
+    assert np.array_equal(aw.t.numpy(), want[0]) and np.array_equal(bw.t.numpy(), want[1])
+    assert len(gemms) == 2
+    ip, ix = g.numpy()
+    out = ex._pushdown_mm(mm, 2)
+    assert len(gemms) == 2  # both products of this run are reused
+    assert np.array_equal(out.t.numpy(), isa_ref.apply_edge(ip, ix, "ADD", None, want[0].astype(np.float64), "dst",
+                                                            want[1].astype(np.float64), "src", False).astype(np.float32))
+    del gemms[:]
+    ex = pushdown_executor(g, a, a, W)  # DGN op 3: x[dst] + x[src] of one table share one GEMM
+    ex._pushdown_mm(mm, 2)
+    assert len(gemms) == 1
+
+
 EXPR_SHAPES = {("DGN", False): (3, False, ["ADD", "ADD", "ADD"]), ("DGN", True): (3, False, ["ADD", "ADD", "ADD"]),
                ("PNA", False): (2, True, ["ADD", "ADD"]), ("PNA", True): (2, True, ["ADD", "ADD"])}
 
