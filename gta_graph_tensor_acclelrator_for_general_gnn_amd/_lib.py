@@ -18,6 +18,7 @@ DIR_R, DIR_C = 0, 1
 IDX_EDGE, IDX_SRC, IDX_DST = 0, 1, 2
 OK, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED = 0, -1, -2, -3
 RED_ADD, RED_MAX, RED_MIN = 0, 1, 2
+MR_MEAN, MR_MAX, MR_MIN, MR_VAR, MR_STD = 1, 2, 4, 8, 16  # gta_reduce_multi's which bits
 BIN_NONE, BIN_ADD, BIN_MUL, BIN_DIV, BIN_SUB = 0, 1, 2, 3, 4
 SF = {"NONE": 0, "RELU": 1, "EXP_LEAKY_RELU": 2, "ELU": 3, "EXP": 4, "LEAKY_RELU": 5, "SIGMOID": 6,
       "TANH": 7, "RECIP": 8}
@@ -36,6 +37,8 @@ SIGNATURES = {
     "gta_aggregate_expr": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp,
                                   _i64, _vp, _vp]),
     "gta_reduce": (_i32, [_i32, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "gta_reduce_multi": (_i32, [_i32, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, ctypes.c_float, _vp,
+                                _i64, _vp, _vp]),
     "gta_aggregate_plan_bytes": (_i64, [_i64, _i64, _i64]),
     "gta_aggregate_plan_build": (_i32, [_vp, _i64, _i64, _i64, _vp, _i64, _vp]),
     "gta_aggregate_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),

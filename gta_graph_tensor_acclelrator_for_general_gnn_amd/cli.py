@@ -39,6 +39,19 @@ def _flag(v):
     raise argparse.ArgumentTypeError(f"not a boolean: {v!r}")
 
 
+def _aggregator(v):
+    """--aggregator: one name of frontend.AGGREGATORS, or a comma list (PNA) as a tuple."""
+    names = [s.strip().upper() for s in str(v).split(",")]
+    if len(names) == 1:
+        if names[0] not in frontend.AGGREGATORS:
+            raise argparse.ArgumentTypeError(f"{v!r}: one of {', '.join(frontend.AGGREGATORS)}, or a comma list for PNA")
+        return names[0]
+    if len(set(names)) != len(names) or any(n not in frontend.MULTI_AGGREGATORS for n in names):
+        raise argparse.ArgumentTypeError(f"{v!r}: a comma list holds distinct names of "
+                                         f"{', '.join(frontend.MULTI_AGGREGATORS)}")
+    return tuple(names)
+
+
 def parser():
     p = argparse.ArgumentParser(prog="python -m gta_graph_tensor_acclelrator_for_general_gnn_amd",
                                 description="compile -> instruction stream -> GPU execution (start.py's flow)")
@@ -50,8 +63,9 @@ def parser():
     p.add_argument("--layers", default="1,2,3", help="genGraphOP layers to run (default 1,2,3)")
     p.add_argument("--feature", type=int, default=None, help="input width (default: the dataset's)")
     p.add_argument("--heads", type=int, default=16, help="attention heads (GAT)")
-    p.add_argument("--aggregator", default="ADD", choices=list(frontend.AGGREGATORS),
-                   help="reduce function of the message gathers (their COMP_TYPE); GAT takes ADD only")
+    p.add_argument("--aggregator", default="ADD", type=_aggregator, metavar="{" + ",".join(frontend.AGGREGATORS) + "}",
+                   help="reduce function of the message gathers (their COMP_TYPE); GAT takes ADD only.  PNA also "
+                        "takes a comma list, e.g. MEAN,MAX,MIN,STD: every aggregator over the same messages, one launch")
     p.add_argument("--stable-softmax", action="store_true",
                    help="overflow-safe attention softmax: exp(score - row max) (GAT; off: the unshifted kernels)")
     p.add_argument("--gather-dtype", choices=["f32", "bf16"], default="f32",
@@ -78,7 +92,9 @@ def run(args, device, log=print):
     for L in layer_ids:
         records = frontend.gen_ops(args.network, L, g.n_rows, g.nnz, feature, args.isReorder, args.heads,
                                    getattr(args, "aggregator", "ADD"))
-        cands = compiler.search(records, g.n_rows, *meta, pingpang=args.isPingpang, sinput=args.isSinput)
+        # (a tuple aggregator's graph: no search, pipeline.Layer takes its default partition)
+        cands = [] if isinstance(getattr(args, "aggregator", "ADD"), tuple) else \
+            compiler.search(records, g.n_rows, *meta, pingpang=args.isPingpang, sinput=args.isSinput)
         kw = dict(reorder=args.isReorder, heads=args.heads, metadata=meta, pingpang=args.isPingpang,
                   sinput=args.isSinput, aggregator=getattr(args, "aggregator", "ADD"),
                   stable_softmax=getattr(args, "stable_softmax", False))
@@ -143,7 +159,11 @@ def run(args, device, log=print):
 
 
 def main(argv=None):
-    args = parser().parse_args(argv)
+    p = parser()
+    args = p.parse_args(argv)
+    if isinstance(args.aggregator, tuple) and args.network != "PNA":
+        p.error(f"--aggregator {','.join(args.aggregator)}: a comma list is PNA's (several aggregators of the same "
+                f"messages); {args.network} takes one name")
     if not torch.cuda.is_available():
         print("error: no HIP device: the layers run on libgta's kernels only", file=sys.stderr)
         return 2

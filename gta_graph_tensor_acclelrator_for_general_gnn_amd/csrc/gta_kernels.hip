@@ -726,6 +726,257 @@ k_reduce_combine(PlanView plan, int F, uint32_t sbit, float* __restrict__ y, int
 }
 
 // ---------------------------------------------------------------------------
+// K2'' multi-reducer: one pass over a row's edges fills MEAN / MAX / MIN / VAR / STD
+// (gta_reduce_multi, PNA's aggregators over the same messages).
+//   k_reduce's skeleton with up to four accumulator sets per column, specialised at compile time
+//   on MOM (the moments s1, s2) and EXT (the extrema), so no instantiation carries dead ones; which
+//   outputs are stored is a wave-uniform run-time choice (a NULL pointer in MultiOut).
+//   Moments: about the shift k(i, c) = the operand value at the row's FIRST edge (CSR position
+//   indptr[i]): s1 = sum (x - k), s2 = sum (x - k)^2 in fp32, then MEAN = k + s1/d,
+//   VAR = max(s2/d - (s1/d)^2, 0), STD = sqrt(VAR + eps).  The terms are the spread's size, not the
+//   mean's, so the subtraction in VAR cancels nothing that matters (the unshifted E[x^2] - E[x]^2
+//   loses every digit once |mean| >> std).  An item of a split row reads the row's first edge
+//   itself, so all of a row's items use one k and their partial sums add up.
+//   Extrema: red_max as in k_reduce; MIN is carried as max(-x) in its own accumulator, the same
+//   compare on the same values, so both are bitwise gta_reduce's.
+//   A sum s2 that is not finite (a +-inf operand, or squares past fp32) makes the three moment
+//   outputs NaN.  A row without edges gets 0 in every output, decided by its degree.
+//   Split rows store P = 2 MOM + 2 EXT planes of partials ([items, F] each, pstride apart):
+//   s1, s2, then max, max(-x); k_reduce_multi_combine sums / folds them in item order.
+// ---------------------------------------------------------------------------
+enum { MR_MEAN = 0, MR_MAX = 1, MR_MIN = 2, MR_VAR = 3, MR_STD = 4, MR_N = 5 };
+struct MultiOut {  // the outputs in GTA_MR_* bit order; y NULL: not requested
+  float* y[MR_N];
+  int64_t ld[MR_N];
+};
+
+struct Moments {
+  float mean, var, sd;
+};
+__device__ __forceinline__ Moments moments_of(float k, float s1, float s2, float deg, float eps) {
+  const float bad = s2 - s2;  // 0, or NaN once s2 is not finite
+  const float m = s1 / deg;
+  float var = s2 / deg - m * m;
+  var = (var < 0.f ? 0.f : var) + bad;  // the select keeps a NaN
+  return {k + m + bad, var, sqrtf(var + eps)};
+}
+
+// the row of x that holds row's shift: the operand of its first edge (CSR position first)
+template <int XMODE>
+__device__ __forceinline__ int64_t shift_row(const int32_t* __restrict__ indices, int64_t first, int64_t row,
+                                             int x_is_row) {
+  if (XMODE == XM_EDGE) return first;
+  return x_is_row ? row : static_cast<int64_t>(indices[first]);
+}
+
+template <int LPE, int VW, int NV, int XMODE, bool MOM, bool EXT, typename TX = float>
+__global__ void __launch_bounds__(kBlock)
+k_reduce_multi(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows, PlanView plan,
+               int use_plan, int x_is_row, const TX* __restrict__ x, int64_t ldx, int F, MultiOut out, float eps,
+               float* __restrict__ partial, int64_t pstride) {
+  constexpr int EPI = kWave / LPE;  // edges per wave instruction
+  constexpr int XB = NV * VW * static_cast<int>(sizeof(TX));
+  constexpr int UR = (64 / XB) < 2 ? 2 : ((64 / XB) > 8 ? 8 : 64 / XB);  // ~64 B of rows in flight per lane
+  constexpr int STEP = UR * EPI;
+  constexpr uint32_t kSign = 0x80000000u;
+  const float ident = -__builtin_inff();
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t item = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  const int64_t n_items = use_plan ? plan.hdr[0] : n_rows;
+  if (item >= n_items) return;
+
+  const auto [row, eb, ee, split] = work_item(indptr, plan, use_plan, item);
+  const bool empty = eb >= ee;  // a whole row without edges (an item of a split row is never empty)
+  const int sub = (LPE == kWave) ? 0 : lane / LPE;
+  const int cl = (LPE == kWave) ? lane : lane % LPE;
+  const float deg = static_cast<float>(ee - eb);  // a row in one item: its degree
+
+  for (int c0 = 0; c0 < F; c0 += LPE * VW * NV) {
+    int col[NV], lo[NV];
+    bool cval[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const Piece p = piece_at<VW>(c0 + (v * LPE + cl) * VW, F);
+      col[v] = p.col; lo[v] = p.lo; cval[v] = p.valid;
+    }
+    float s1[NV][VW], s2[NV][VW], amx[NV][VW], amn[NV][VW];
+    Vec<VW> kv[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int k = 0; k < VW; ++k) {
+        s1[v][k] = 0.f; s2[v][k] = 0.f; kv[v].v[k] = 0.f;
+        amx[v][k] = ident; amn[v][k] = ident;
+      }
+    if (MOM && !empty) {
+      const TX* kp = x + shift_row<XMODE>(indices, split ? indptr[row] : eb, row, x_is_row) * ldx;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) load_row(kv[v], kp + col[v]);
+    }
+
+    const bool use_idx = (XMODE == XM_IDX) && !x_is_row;
+    int idxv = 0;
+    if (use_idx && eb < ee) idxv = indices[min(eb + lane, ee - 1)];
+    for (int64_t e0 = eb; e0 < ee; e0 += kWave) {
+      const int n = static_cast<int>(min<int64_t>(kWave, ee - e0));
+      int idxn = 0;
+      if (use_idx) idxn = indices[min(e0 + kWave + lane, ee - 1)];  // clamped: the load is unconditional
+      for (int s = 0; s < n; s += STEP) {
+        Vec<VW> xv[UR][NV];
+        bool valid[UR];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+          const int j = s + u * EPI + sub;
+          valid[u] = j < n;
+          const int jj = j < n ? j : n - 1;
+          const TX* xp = x + gather_row<LPE, XMODE>(e0, jj, row, x_is_row, idxv) * ldx;
+#pragma unroll
+          for (int v = 0; v < NV; ++v) load_row(xv[u][v], xp + col[v]);
+        }
+#pragma unroll
+        for (int u = 0; u < UR; ++u)
+#pragma unroll
+          for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int k = 0; k < VW; ++k) {
+              const float t = xv[u][v].v[k];
+              if constexpr (MOM) {
+                const float d = valid[u] ? t - kv[v].v[k] : 0.f;
+                s1[v][k] += d;
+                s2[v][k] = fmaf(d, d, s2[v][k]);
+              }
+              if constexpr (EXT) {
+                amx[v][k] = red_max(amx[v][k], valid[u] ? t : ident);
+                amn[v][k] = red_max(amn[v][k], valid[u] ? red_flip(t, kSign) : ident);
+              }
+            }
+      }
+      idxv = idxn;
+    }
+    if (LPE < kWave) {  // fold the EPI edge slots: the sums add, the extrema fold with the reducer
+#pragma unroll
+      for (int off = LPE; off < kWave; off <<= 1)
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+#pragma unroll
+          for (int k = 0; k < VW; ++k) {
+            if constexpr (MOM) {
+              s1[v][k] += __shfl_xor(s1[v][k], off);
+              s2[v][k] += __shfl_xor(s2[v][k], off);
+            }
+            if constexpr (EXT) {
+              amx[v][k] = red_max(amx[v][k], __shfl_xor(amx[v][k], off));
+              amn[v][k] = red_max(amn[v][k], __shfl_xor(amn[v][k], off));
+            }
+          }
+    }
+    if (sub == 0) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        if (!cval[v]) continue;
+        Vec<VW> o;
+        if (split) {  // the planes of partials: sums as they are, both extrema in the max domain
+          float* pp = partial + item * static_cast<int64_t>(F) + col[v];
+          if constexpr (MOM) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = s1[v][k];
+            store_piece(o, pp, lo[v]);
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = s2[v][k];
+            store_piece(o, pp + pstride, lo[v]);
+            pp += 2 * pstride;
+          }
+          if constexpr (EXT) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = amx[v][k];
+            store_piece(o, pp, lo[v]);
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = amn[v][k];
+            store_piece(o, pp + pstride, lo[v]);
+          }
+          continue;
+        }
+        if constexpr (MOM) {
+          Moments m[VW];
+#pragma unroll
+          for (int k = 0; k < VW; ++k) m[k] = moments_of(kv[v].v[k], s1[v][k], s2[v][k], deg, eps);
+          if (out.y[MR_MEAN]) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = empty ? 0.f : m[k].mean;
+            store_piece(o, out.y[MR_MEAN] + row * out.ld[MR_MEAN] + col[v], lo[v]);
+          }
+          if (out.y[MR_VAR]) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = empty ? 0.f : m[k].var;
+            store_piece(o, out.y[MR_VAR] + row * out.ld[MR_VAR] + col[v], lo[v]);
+          }
+          if (out.y[MR_STD]) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = empty ? 0.f : m[k].sd;
+            store_piece(o, out.y[MR_STD] + row * out.ld[MR_STD] + col[v], lo[v]);
+          }
+        }
+        if constexpr (EXT) {
+          if (out.y[MR_MAX]) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = empty ? 0.f : amx[v][k];
+            store_piece(o, out.y[MR_MAX] + row * out.ld[MR_MAX] + col[v], lo[v]);
+          }
+          if (out.y[MR_MIN]) {
+#pragma unroll
+            for (int k = 0; k < VW; ++k) o.v[k] = empty ? 0.f : red_flip(amn[v][k], kSign);
+            store_piece(o, out.y[MR_MIN] + row * out.ld[MR_MIN] + col[v], lo[v]);
+          }
+        }
+      }
+    }
+  }
+}
+
+// split rows: sum the two planes of moment partials in item order and fold the two planes of
+// extrema (k_reduce_combine's fold), then the same epilogue; the row's shift is read again
+template <bool MOM, bool EXT, typename TX>
+__global__ void __launch_bounds__(kBlock)
+k_reduce_multi_combine(PlanView plan, const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
+                       int x_mode, const TX* __restrict__ x, int64_t ldx, int F, MultiOut out, float eps,
+                       const float* __restrict__ partial, int64_t pstride) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t s = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  if (s >= plan.hdr[1]) return;
+  const int64_t row = plan.split_row[s];
+  const int64_t first = plan.split_first[s];
+  const int cnt = plan.split_cnt[s];
+  const int64_t e = indptr[row];
+  const float deg = static_cast<float>(indptr[row + 1] - e);  // a split row has edges
+  const TX* kp = x;
+  if (MOM) kp += (x_mode == GTA_IDX_EDGE ? e : (x_mode == GTA_IDX_DST ? row : static_cast<int64_t>(indices[e]))) * ldx;
+  for (int c = lane; c < F; c += kWave) {
+    const float* pp = partial + first * F + c;
+    if constexpr (MOM) {
+      float s1 = 0.f, s2 = 0.f;
+      for (int j = 0; j < cnt; ++j) {
+        s1 += pp[static_cast<int64_t>(j) * F];
+        s2 += pp[pstride + static_cast<int64_t>(j) * F];
+      }
+      const Moments m = moments_of(load_elem(kp + c), s1, s2, deg, eps);
+      if (out.y[MR_MEAN]) out.y[MR_MEAN][row * out.ld[MR_MEAN] + c] = m.mean;
+      if (out.y[MR_VAR]) out.y[MR_VAR][row * out.ld[MR_VAR] + c] = m.var;
+      if (out.y[MR_STD]) out.y[MR_STD][row * out.ld[MR_STD] + c] = m.sd;
+      pp += 2 * pstride;
+    }
+    if constexpr (EXT) {
+      float amx = -__builtin_inff(), amn = -__builtin_inff();
+      for (int j = 0; j < cnt; ++j) {
+        amx = red_max(amx, pp[static_cast<int64_t>(j) * F]);
+        amn = red_max(amn, pp[pstride + static_cast<int64_t>(j) * F]);
+      }
+      if (out.y[MR_MAX]) out.y[MR_MAX][row * out.ld[MR_MAX] + c] = amx;
+      if (out.y[MR_MIN]) out.y[MR_MIN][row * out.ld[MR_MIN] + c] = red_flip(amn, 0x80000000u);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Lean aggregate for rows that exactly fill a wavefront (F = 64 * VW): one edge
 // per wave instruction, wave-uniform row base.  Per unrolled step of U edges:
 //   * U row loads issued back to back, no per-edge validity select (full steps
@@ -5156,6 +5407,111 @@ int check_heads(const char* who, int64_t heads, int sf, bool need_exp, int64_t l
   if (lda < heads || ldb < heads) return fail(GTA_ERR_ARG, std::string(who) + ": leading dimension < heads");
   return GTA_OK;
 }
+
+// host-side dispatch of k_reduce_multi (gta_reduce_multi): reduce_impl's shape, ladder and combine
+// pattern, specialised on which accumulator families the call needs
+template <int LPE, int VW, int NV, int XM, typename TX>
+void launch_multi(bool mom, bool ext, const AggArgs& a, const MultiOut& out, float eps, int64_t pstride,
+                  int64_t n_items_bound, hipStream_t s) {
+  const int64_t blocks = (n_items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
+  with_bools([&](auto M, auto E) {
+    if constexpr ((M() || E()) && !(M() && VW == 8))  // (the 16-B bf16 pieces carry the extrema only)
+      k_reduce_multi<LPE, VW, NV, XM, M(), E(), TX><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(
+          a.indptr, a.indices, a.n_rows, a.plan, a.use_plan, a.x_is_row, static_cast<const TX*>(a.x), a.ldx, a.F, out,
+          eps, a.partial, pstride);
+  }, mom, ext);
+}
+
+template <int LPE, int VW, int NV>
+bool dispatch_multi_x(int xm, bool bf, bool mom, bool ext, const AggArgs& a, const MultiOut& out, float eps,
+                      int64_t pstride, int64_t nb, hipStream_t s) {
+  if (bf) {  // bf16 rows are gathered by index only
+    if (xm != XM_IDX) return false;
+    launch_multi<LPE, VW, NV, XM_IDX, uint16_t>(mom, ext, a, out, eps, pstride, nb, s);
+  } else if (xm == XM_EDGE) {
+    launch_multi<LPE, VW, NV, XM_EDGE, float>(mom, ext, a, out, eps, pstride, nb, s);
+  } else {
+    launch_multi<LPE, VW, NV, XM_IDX, float>(mom, ext, a, out, eps, pstride, nb, s);
+  }
+  return true;
+}
+
+int reduce_multi_impl(int which, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
+                      int x_mode, const void* x, int64_t ldx, int64_t F, int x_dtype, float* const* ys,
+                      const int64_t* ldys, float std_eps, const void* plan, int64_t plan_chunk, void* workspace,
+                      void* stream) {
+  const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
+  constexpr int kAll = GTA_MR_MEAN | GTA_MR_MAX | GTA_MR_MIN | GTA_MR_VAR | GTA_MR_STD;
+  if (which == 0 || (which & ~kAll)) return fail(GTA_ERR_ARG, "reduce_multi: which must be a non-empty set of GTA_MR_* bits");
+  if (n_rows < 0 || nnz < 0 || F <= 0) return fail(GTA_ERR_ARG, "reduce_multi: bad sizes");
+  if (x_mode != GTA_IDX_EDGE && x_mode != GTA_IDX_SRC && x_mode != GTA_IDX_DST)
+    return fail(GTA_ERR_ARG, "reduce_multi: bad x_mode");
+  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, "reduce_multi: x_dtype must be F32 or BF16");
+  const bool bf = x_dtype == GTA_BF16;
+  const int xe = bf ? 2 : 4;  // bytes per x element
+  if (bf && x_mode == GTA_IDX_EDGE)
+    return fail(GTA_ERR_UNSUPPORTED, "reduce_multi: bf16 rows are gathered by index (SRC / DST)");
+  if (F > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, "reduce_multi: F too large");
+  if (!ys || !ldys) return fail(GTA_ERR_ARG, "reduce_multi: ys / ldys is NULL");
+  MultiOut out{};
+  float* y0 = nullptr;
+  int64_t ldy0 = 0;
+  for (int b = 0, k = 0; b < MR_N; ++b) {  // one entry per set bit, in bit order
+    if (!(which >> b & 1)) continue;
+    if (!ys[k] || ldys[k] < F) return fail(GTA_ERR_ARG, "reduce_multi: an output is NULL or its row stride < F");
+    out.y[b] = ys[k]; out.ld[b] = ldys[k];
+    if (!y0) { y0 = ys[k]; ldy0 = ldys[k]; }
+    ++k;
+  }
+  if (n_rows == 0) return GTA_OK;
+  // with no edges, x and indices are never read (may be NULL); every row gets 0
+  if (!indptr || (nnz > 0 && !x) || (nnz > 0 && ldx < F)) return fail(GTA_ERR_ARG, "reduce_multi: bad arguments");
+  if (x_mode == GTA_IDX_SRC && !indices && nnz > 0) return fail(GTA_ERR_ARG, "reduce_multi: x_mode SRC needs indices");
+  if (nnz == 0) { x = y0; ldx = ldy0; }  // any valid address: no row has an edge to read
+  const int xm = (x_mode == GTA_IDX_EDGE) ? XM_EDGE : XM_IDX;
+  auto outs_ok = [&](int vw, int bytes) {  // every requested output's rows aligned to vw floats / bytes
+    for (int b = 0; b < MR_N; ++b)
+      if (out.y[b] && (out.ld[b] % vw || !aligned(out.y[b], bytes))) return false;
+    return true;
+  };
+  auto ok_vw = [&](int vw) { return !(F % vw || ldx % vw || !aligned(x, xe * vw)) && outs_ok(vw, 4 * vw); };
+  const bool mom = which & (GTA_MR_MEAN | GTA_MR_VAR | GTA_MR_STD), ext = which & (GTA_MR_MAX | GTA_MR_MIN);
+  // The extrema do not depend on the order of the edges and take reduce_impl's shapes.  The moments'
+  // sums do (each of a form's edge slots adds up its own edges): with them the shape comes from F
+  // and the layout alone -- the fp32 ladder, no 16-B bf16 pieces -- so a bf16 table gives bitwise
+  // the fp32 call on its widened rows
+  const bool vw8_ok = !mom && nnz > 0 && !tuning().force_vw && ldx % 4 == 0 && aligned(x, 8) && outs_ok(4, 16);
+  const GatherShape g = gather_shape(F, bf && !mom, ok_vw, /*lpe_knob=*/false, vw8_ok);
+  AggArgs a{};
+  const int64_t bound = gather_args(a, "reduce_multi", indptr, indices, n_rows, nnz, x_mode, x, ldx, F, y0, ldy0, plan,
+                                    plan_chunk, workspace);
+  if (bound < 0) return static_cast<int>(bound);
+  const int64_t pstride = bound * F;  // one plane of partials: gta_aggregate_workspace_bytes(..., F)
+  hipStream_t s = S(stream);
+  bool ok;
+  if (g.vw8) {
+    ok = dispatch_lpe<8>(g.lpe, 1, [&](auto, auto L, auto) {
+      launch_multi<L(), 8, 1, XM_IDX, uint16_t>(mom, ext, a, out, std_eps, pstride, bound, s);
+      return true;
+    });
+  } else {
+    ok = dispatch_vw(g.vw, g.lpe, g.nv, [&](auto V, auto L, auto N) {
+      return dispatch_multi_x<L(), V(), N()>(xm, bf, mom, ext, a, out, std_eps, pstride, bound, s);
+    });
+  }
+  if (!ok) return fail(GTA_ERR_UNSUPPORTED, "reduce_multi: no kernel variant");
+  GTA_LAUNCHED("k_reduce_multi");
+  const bool combined = plan && launch_combine(nnz, plan_chunk, [&](dim3 grid) {
+    with_bools([&](auto M, auto E, auto B) {
+      using TX = std::conditional_t<B(), uint16_t, float>;
+      if constexpr (M() || E())
+        k_reduce_multi_combine<M(), E(), TX><<<grid, dim3(kBlock), 0, s>>>(
+            a.plan, indptr, indices, x_mode, static_cast<const TX*>(x), ldx, a.F, out, std_eps, a.partial, pstride);
+    }, mom, ext, bf);
+  });
+  if (combined) GTA_LAUNCHED("k_reduce_multi_combine");
+  return GTA_OK;
+}
 }  // namespace
 extern "C" {
 
@@ -5179,6 +5535,13 @@ int gta_reduce(int red, const int64_t* indptr, const int32_t* indices, int64_t n
     return fail(GTA_ERR_ARG, "reduce: red must be GTA_RED_ADD, GTA_RED_MAX or GTA_RED_MIN");
   return reduce_impl(red, indptr, indices, n_rows, nnz, x_mode, x, ldx, F, x_dtype, y, ldy, plan, plan_chunk,
                      workspace, stream);
+}
+
+int gta_reduce_multi(int which, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
+                     const void* x, int64_t ldx, int64_t F, int x_dtype, float* const* ys, const int64_t* ldys,
+                     float std_eps, const void* plan, int64_t plan_chunk, void* workspace, void* stream) {
+  return reduce_multi_impl(which, indptr, indices, n_rows, nnz, x_mode, x, ldx, F, x_dtype, ys, ldys, std_eps, plan,
+                           plan_chunk, workspace, stream);
 }
 
 int gta_aggregate_expr(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int shape,

@@ -18,7 +18,9 @@ reads the same two YAML files, and runs the stream on real device tensors:
         an edge GEMM + gather (MM);
       - scatters with a STORE_E are materialised with gta_scatter;
       - a gather reduces with its COMP_TYPE: ADD on the aggregate kernels and every fusion above,
-        MAX / MIN on gta_reduce, MEAN on the aggregate with row_scale = 1/deg (_eval_reduce);
+        MAX / MIN on gta_reduce, MEAN on the aggregate with row_scale = 1/deg, VAR / STD on
+        gta_reduce_multi (_eval_reduce); sibling gathers of one producer (a PNA layer's
+        aggregators) are filled by ONE gta_reduce_multi launch (_eval_multi);
   * numerics the YAML leaves open come from semantics.py.
 Returns ExecResult(values per op, outputs of sink ops, elapsed_s, alg_bytes).
 """
@@ -155,6 +157,11 @@ def _memo(cache, key, src, make):
 
 
 REDUCERS = ("MAX", "MIN", "MEAN")  # gather COMP_TYPEs beside the sum (Executor._eval_reduce)
+MOMENTS = ("VAR", "STD")  # and the moment reducers, which only gta_reduce_multi computes (ops.reduce_multi)
+# Smallest group of sibling gathers that takes the one row-chunked multi-reducer launch when every
+# member would have passed the column-blocked gate on its own (a source table beyond L2): the
+# blocked passes are each cheaper there, so a pair stays blocked
+MULTI_MIN_BLOCKED = 3
 
 
 def _mean_scale(g):
@@ -182,7 +189,7 @@ MAX_MATERIALIZE_BYTES = 96 << 30  # refuse to materialise a single edge tensor l
 
 class Executor:
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, dist=None,
-                 softmax_shift=None, gather_dtype=None):
+                 softmax_shift=None, gather_dtype=None, multi_reduce=True):
         self.g = opgraph
         # dist (distributed.Comm): node tensors are this rank's row block; gathers are
         # reduce-scattered to it and dst-side scatters all-gather it (distributed.py)
@@ -217,6 +224,14 @@ class Executor:
         #   ops.reduce_blocked (values identical to ops.reduce's: every output is one of its inputs);
         #   False keeps the row-chunked gta_reduce (A/B)
         self.reduce_blocked = True
+        #   multi_reduce: sibling gathers (rewrites.sibling_gathers: same producer, same ORDER, COMP_TYPEs
+        #   among MEAN / MAX / MIN / VAR / STD) are filled by one ops.reduce_multi launch when the first
+        #   of them is evaluated -- the messages are read once; False: one launch per gather (A/B).
+        #   MAX / MIN are the single launches' values, the moments within their rounding bound.
+        self.multi_reduce = bool(multi_reduce)
+        self.std_eps = 1e-5  # STD = sqrt(VAR + std_eps)
+        self.siblings = {i: grp for grp in rewrites.sibling_gathers(opgraph) for i in grp}
+        self._multi_vals = {}  # sibling gather -> its value from the group's launch, until it is evaluated
         # the graph rewrites below are matched once, by rewrites.py (pure functions of the op graph)
         self.consumers = cons = rewrites.consumers_of(opgraph)
         #   fuse_softmax: GAT's score -> SF -> per-row sum (-> divide) chain runs as one
@@ -807,7 +822,7 @@ class Executor:
         MM on the node side; anything else is materialised as an edge tensor and summed.
         self_term (x, s): y = x * s + the aggregate, or None if this gather's form cannot take it;
         out_dtype (self_term only): y's storage dtype."""
-        if op.comp in REDUCERS:  # COMP_TYPE MAX / MIN / MEAN: no accumulate, no self term, none of the sum's fusions
+        if op.comp in REDUCERS + MOMENTS:  # not the sum: no accumulate, no self term, none of the sum's fusions
             return None if (acc is not None or self_term is not None) else self._eval_reduce(op)
         if op.order == "C" and (acc is not None or self_term is not None):
             return None  # ORDER C takes no accumulator and no self term
@@ -894,7 +909,9 @@ class Executor:
         node table (fp32 or bf16; no [E, F] tensor); everything else -- an edge tensor, or a fused
         applyedge MUL / MM producer, which is first formed as the unfused op forms it -- in EDGE
         mode.  MAX / MIN run gta_reduce; MEAN is the plain ADD aggregate with row_scale = 1 / deg
-        (empty rows 0; ORDER C: the out-degree from colptr).  None of the rewrites that rely on the
+        (empty rows 0; ORDER C: the out-degree from colptr); VAR / STD (MOMENTS) run gta_reduce_multi
+        with one member; a gather of a sibling group (self.siblings) runs the group's one launch, or
+        takes the value that launch left for it (_eval_multi).  None of the rewrites that rely on the
         gather being a sum applies (mm_first, two_hop, gather_acc, the weighted aggregate, the
         attention chains, edge_expr)."""
         d = self.dist
@@ -902,12 +919,21 @@ class Executor:
             raise NotImplementedError(
                 f"op {op.idx}: gather {op.comp} on a shard that holds only part of each output node's edges "
                 "(partial maxima / means cannot be summed across ranks); row-local shards of an ORDER R gather work")
+        if op.idx in self._multi_vals:  # a sibling's launch filled it
+            return self._multi_vals.pop(op.idx)
         v = self._source(op, 0)
         if isinstance(v, Deferred):
             v = self._materialize_deferred(v)
         scat, col = isinstance(v, Scat), op.order == "C"
         g, t, mode, n_out = self._site(v, op.order)
         E, F = self.graph.nnz, t.shape[1]
+        group = self.siblings.get(op.idx) if self.multi_reduce else None
+        if group is not None and self._multi_wanted(group, v, t, g, col):
+            return self._eval_multi(op, group, g, t, mode, n_out, index=col or scat, row_es=t.element_size() if col else 4)
+        if op.comp in MOMENTS:  # one member: the same kernel family, the moment accumulators only
+            y, = ops.reduce_multi(g, t, (op.comp,), mode, plan=self._plan(), std_eps=self.std_eps)
+            self._count(self._gather_bytes(E, n_out, F, t.element_size() if col else 4, index=col or scat))
+            return NodeT(y)
         # (ORDER C charges the table's own element size, ORDER R 4 bytes; EDGE mode of the CSR reads no index)
         nbytes = self._gather_bytes(E, n_out, F, t.element_size() if col else 4, index=col or scat)
         # column-blocked when a source-gathered node table outgrows L2 (_spmm's gate, evaluated before
@@ -935,6 +961,36 @@ class Executor:
             y = ops.reduce(g, t, op.comp, mode, plan=self._plan())
         self._count(nbytes)
         return NodeT(y)
+
+    def _would_block(self, comp, v, t, g, col):
+        """_eval_reduce's column-blocked gate for one gather of COMP_TYPE comp reading v (table t)."""
+        if not (self.reduce_blocked and isinstance(v, Scat)) or comp in MOMENTS:
+            return False
+        if not col and v.mode == "src" and (comp != "MEAN" or self.gather_dtype == torch.bfloat16):
+            return bool(self._blocked_blocks(t, "src", 0))
+        if col and v.mode == "dst" and comp != "MEAN":
+            return bool(self._blocked_blocks(t, "src", 0, g))
+        return False
+
+    def _multi_wanted(self, group, v, t, g, col):
+        """The group launch runs row-chunked only.  Where every member would take the column-blocked
+        form on its own, the one pass replaces len(group) cheaper ones: from MULTI_MIN_BLOCKED members."""
+        if len(group) >= MULTI_MIN_BLOCKED:
+            return True
+        return not all(self._would_block(self.g.ops[i].comp, v, t, g, col) for i in group)
+
+    def _eval_multi(self, op, group, g, t, mode, n_out, index, row_es):
+        """Every gather of op's sibling group from ONE ops.reduce_multi launch (op: the first of them
+        to be evaluated); the others find their value in _multi_vals.  Bytes: the operand read once,
+        one output per member."""
+        reds = tuple(self.g.ops[i].comp for i in group)
+        ys = ops.reduce_multi(g, t, reds, mode, plan=self._plan(), std_eps=self.std_eps)
+        E, F = self.graph.nnz, t.shape[1]
+        self._count(self._gather_bytes(E, n_out, F, row_es, index=index) + (len(group) - 1) * n_out * 4 * F)
+        for i, y in zip(group, ys):
+            if i != op.idx:
+                self._multi_vals[i] = NodeT(y)
+        return NodeT(ys[group.index(op.idx)])
 
     def _weighted_aggregate(self, u, v, acc=None, self_term=None, out_dtype=torch.float32, order="R"):
         """sum_e u(e) (.) v(e) over each output node's edges (_site): the wider operand is the feature

@@ -146,7 +146,47 @@ def _size(sym, env):
     return v * 4
 
 
-AGGREGATORS = ("ADD", "MAX", "MIN", "MEAN")  # COMP_TYPE values of a message gather (ADD: genGraphOP's)
+# COMP_TYPE values of a message gather (ADD: genGraphOP's; VAR / STD: the population variance and
+# sqrt(VAR + eps) of the messages, PNA's fourth aggregator)
+AGGREGATORS = ("ADD", "MAX", "MIN", "MEAN", "VAR", "STD")
+MULTI_AGGREGATORS = ("MEAN", "MAX", "MIN", "VAR", "STD")  # what a tuple aggregator (PNA) may hold
+
+_PNA_GATHER, _PNA_TAIL = 8, (9, 10)  # PNA's message gather and its tail (the scaler MUL, the MM) in both tables
+
+
+def pna_clones(k):
+    """{op of the expanded PNA graph: the op of TABLE's PNA it is a copy of} for a tuple aggregator
+    of k members: gathers 8 .. 7+k (of op 8), scaler MULs 8+k .. 7+2k (of op 9), MMs 8+2k .. 7+3k
+    (of op 10).  The k-1 ADDs that sum the MM outputs (8+3k ..) are new ops, copies of none."""
+    out = {}
+    for j in range(k):
+        out[8 + j], out[8 + k + j], out[8 + 2 * k + j] = 8, 9, 10
+    return out
+
+
+def _pna_rows(rows, aggs):
+    """PNA's rows with the message gather (op 8) as one sibling gather of op 7 per aggregator, each
+    with its own clone of the tail (MUL op 9, MM op 10), the MM outputs summed by a chain of
+    applynode ADDs: concat(a_1 .. a_K) W = sum_k a_k W_k, written with the ops the ISA has (it has
+    no concat).  New ops are numbered consecutively after op 7 (pna_clones)."""
+    k = len(aggs)
+    head = [r for r in rows if r[0] < _PNA_GATHER]
+    g8, m9, m10 = (next(r for r in rows if r[0] == i) for i in (_PNA_GATHER,) + _PNA_TAIL)
+    G, M, W, A = 8, 8 + k, 8 + 2 * k, 8 + 3 * k  # first gather, MUL, MM and ADD
+    out = [r if r[0] != 7 else r[:10] + ([G + j for j in range(k)],) + r[11:] for r in head]
+
+    def clone(r, no, ins, outs, comp=None):
+        return (no, comp or r[1], r[2], r[3], r[4], ins, r[6], r[7], r[8], r[9], outs, r[11], r[12])
+
+    out += [clone(g8, G + j, [7], [M + j], comp=aggs[j]) for j in range(k)]
+    out += [clone(m9, M + j, [G + j], [W + j]) for j in range(k)]
+    # MM j feeds ADD max(j - 1, 0): the chain's first ADD sums MMs 0 and 1, each later one adds the next MM
+    out += [clone(m10, W + j, [M + j], [A + max(j - 1, 0)]) for j in range(k)]
+    for j in range(k - 1):
+        ins = [W, W + 1] if j == 0 else [A + j - 1, W + j + 1]
+        out.append(_r(A + j, "ADD", "applynode", "R", [_N, _N], ins, 2, 0, None, ["fout", "fout"],
+                      [] if j == k - 2 else [A + j + 1], _N, "fout"))
+    return out
 
 
 def gen_ops(network, layer, node_num, edge_num, feature, reorder=False, heads=16, aggregator="ADD"):
@@ -154,14 +194,25 @@ def gen_ops(network, layer, node_num, edge_num, feature, reorder=False, heads=16
 
     aggregator: the reduce function of the network's message gathers -- the gather op's COMP_TYPE
     (the ISA gather carries it as a field: COMPUTE mul: add, template/ISA_defination.yaml:58-61).
-    "ADD" is genGraphOP's output unchanged; "MAX" / "MIN" / "MEAN" rewrite the COMP_TYPE of every
-    gather of the layer (both hops of SGC) and nothing else: GraphSAGE-pool's max, PNA's max / min
-    / mean, GCN- and SAGE-mean.  GAT's gathers are its softmax sums, not a message reducer: any
-    other aggregator than ADD raises ValueError."""
+    "ADD" is genGraphOP's output unchanged; "MAX" / "MIN" / "MEAN" / "VAR" / "STD" rewrite the
+    COMP_TYPE of every gather of the layer (both hops of SGC) and nothing else: GraphSAGE-pool's
+    max, PNA's max / min / mean / std, GCN- and SAGE-mean.  GAT's gathers are its softmax sums, not
+    a message reducer: any other aggregator than ADD raises ValueError.
+    A tuple or list (PNA only, e.g. ("MEAN", "MAX", "MIN", "STD"): distinct names of
+    MULTI_AGGREGATORS, at least two) applies every member to the same messages: op 8 becomes one
+    sibling gather of op 7 per member, each with its own scaler MUL and MM, summed by an ADD chain
+    (_pna_rows; pna_clones names what each new op copies)."""
     key = (network, bool(reorder))
     rows = TABLE.get(key, TABLE.get(network))
     if rows is None:
         raise ValueError(f"no such network {network}")
+    if isinstance(aggregator, (tuple, list)):
+        aggs = tuple(aggregator)
+        if network != "PNA":
+            raise ValueError(f"a tuple aggregator is PNA's (several aggregators of the same messages); {network} takes one name")
+        if len(aggs) < 2 or len(set(aggs)) != len(aggs) or any(a not in MULTI_AGGREGATORS for a in aggs):
+            raise ValueError(f"a tuple aggregator holds two or more distinct names of {MULTI_AGGREGATORS} (got {aggs!r})")
+        rows, aggregator = _pna_rows(rows, aggs), "ADD"  # (the gathers carry their COMP_TYPE already)
     if aggregator not in AGGREGATORS:
         raise ValueError(f"aggregator must be one of {AGGREGATORS} (got {aggregator!r})")
     if aggregator != "ADD" and network == "GAT":

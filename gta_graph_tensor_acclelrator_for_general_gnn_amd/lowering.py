@@ -29,7 +29,7 @@ from . import ir
 UNIT_OF = {"ADD": "VEC_ALU", "SF": "SF_ALU", "MUL": "VEC_ALU", "LOAD": "Memory_Access_Unit",
            "LOAD_N": "Virtual_Loader", "STORE": "Memory_Access_Unit", "MM": "MM", "Fused": "MM",
            # the gather's other reducers (frontend.AGGREGATORS): element-wise like ADD, the vector ALU
-           "MAX": "VEC_ALU", "MIN": "VEC_ALU", "MEAN": "VEC_ALU"}
+           "MAX": "VEC_ALU", "MIN": "VEC_ALU", "MEAN": "VEC_ALU", "VAR": "VEC_ALU", "STD": "VEC_ALU"}
 
 
 class _NoAlias(yaml.SafeDumper):

@@ -7,6 +7,8 @@ One function per ISA op / fused pattern of the GTA stream:
                (hardware_info.yaml Inst_fused :35-38, code/interpreter.py:575-636, 764-802) -> gta_aggregate
   reduce       ISA `gather` with COMP_TYPE MAX / MIN: rows without edges 0, NaN propagates, every
                output bitwise one of its inputs (+0 / -0 apart)             -> gta_reduce
+  reduce_multi several reducers of the same gathered rows in one pass: MEAN / MAX / MIN / VAR / STD
+               (PNA's aggregators; the moments about the row's first value)  -> gta_reduce_multi
   reduce_blocked  the same MAX / MIN gather of a node table, column-blocked for tables beyond L2
                (the blocked aggregate's plan and slab rows)                 -> gta_reduce_blocked
   apply_edge   applyedge ADD/MUL/SF (genGraphOP.py:36, 55-60)            -> gta_apply_edge
@@ -278,6 +280,65 @@ def reduce(graph, x, red="MAX", x_mode="src", out=None, plan=None):
                           _ptr(x), ldx, F, x_dt, _ptr(out), ldy, _ptr(pbuf), chunk, _ptr(ws), _stream(x.device)),
           "reduce")
     return out
+
+
+MULTI_REDS = ("MEAN", "MAX", "MIN", "VAR", "STD")  # gta_reduce_multi's outputs, in GTA_MR_* bit order
+_MR_BITS = {"MEAN": _lib.MR_MEAN, "MAX": _lib.MR_MAX, "MIN": _lib.MR_MIN, "VAR": _lib.MR_VAR, "STD": _lib.MR_STD}
+
+
+def reduce_multi_planes(reds):
+    """Planes of partials a reduce_multi call over reds stores for split rows (gta.h's P): two for
+    the moments, two for the extrema."""
+    return 2 * any(r in ("MEAN", "VAR", "STD") for r in reds) + 2 * any(r in ("MAX", "MIN") for r in reds)
+
+
+def reduce_multi(graph, x, reds, x_mode="src", outs=None, out=None, plan=None, std_eps=1e-5):
+    """Several reducers over the same gathered rows in one pass (gta_reduce_multi): PNA's
+    aggregators.  reds: a sequence without duplicates drawn from ("MEAN", "MAX", "MIN", "VAR",
+    "STD"); returns a tuple of [N, F] float32 tensors in reds order.
+
+    MAX / MIN are reduce()'s (NaN propagates, bitwise one of the inputs, independent of plan).  The
+    moments are taken about the shift k(i, c) = the operand value at row i's first edge: with d the
+    degree, s1 = sum (x - k), s2 = sum (x - k)^2 in fp32 in edge order, MEAN = k + s1/d,
+    VAR = max(s2/d - (s1/d)^2, 0) (the population variance), STD = sqrt(VAR + std_eps); the
+    unshifted E[x^2] - E[x]^2 would lose every digit once |mean| >> std.  A row without edges gets 0
+    in every output (STD too); a NaN in a (row, column) makes all its outputs NaN, a +-inf its
+    moment outputs NaN.  A row split by the plan uses one k in all its items and sums the partials
+    in item order (deterministic).
+    outs: None, or one [N, F] float32 tensor per reducer (each with its own row stride).
+    out: None, or [N, len(reds) * F]: the returned tensors are views of its column blocks.
+    x, x_mode, plan, graph (a CSC.view(...) for direction C): as reduce()."""
+    reds = tuple(reds)
+    if not reds or len(set(reds)) != len(reds) or any(r not in _MR_BITS for r in reds):
+        raise ValueError(f"reduce_multi: reds must be distinct names from {MULTI_REDS} (got {reds!r})")
+    if x_mode not in _MODES:
+        raise ValueError(f"reduce_multi: x_mode must be one of {sorted(_MODES)} (got {x_mode!r})")
+    if outs is not None and out is not None:
+        raise ValueError("reduce_multi: give outs or out, not both")
+    _need_gpu(x, out, graph.indptr, *(outs or ()))
+    F, K = x.shape[1], len(reds)
+    ldx, x_dt = _gather_operand(graph, x, x_mode, "reduce_multi")
+    if out is not None:
+        if out.dim() != 2 or out.shape[0] < graph.n_rows or out.shape[1] != K * F:
+            raise ValueError("reduce_multi: out must be [N, len(reds) * F]")
+        outs = tuple(out[:, k * F:(k + 1) * F] for k in range(K))
+    elif outs is None:
+        outs = tuple(torch.empty(graph.n_rows, F, dtype=torch.float32, device=x.device) for _ in reds)
+    outs = tuple(outs)
+    if len(outs) != K or any(o.shape[0] < graph.n_rows or o.shape[1] != F for o in outs):
+        raise ValueError("reduce_multi: one [N, F] output per reducer")
+    lds = [_rows(o, "out") for o in outs]
+    if graph.n_rows == 0:
+        return outs
+    pbuf, ws, chunk = _plan_args(graph, plan, reduce_multi_planes(reds) * F)
+    order = sorted(range(K), key=lambda k: _MR_BITS[reds[k]])  # the ABI takes them in bit order
+    ys = (ctypes.c_void_p * K)(*(outs[k].data_ptr() for k in order))
+    ldys = (ctypes.c_int64 * K)(*(lds[k] for k in order))
+    which = sum(_MR_BITS[r] for r in reds)
+    check(_L().gta_reduce_multi(which, _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz,
+                                _MODES[x_mode], _ptr(x), ldx, F, x_dt, ys, ldys, float(std_eps), _ptr(pbuf), chunk,
+                                _ptr(ws), _stream(x.device)), "reduce_multi")
+    return outs
 
 
 EXPR_SHAPES = {1: 2, 2: 3, 3: 4}  # gta_aggregate_expr shape -> operand count

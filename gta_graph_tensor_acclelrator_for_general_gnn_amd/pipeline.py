@@ -22,8 +22,12 @@ class Layer:
                  stable_softmax=False, gather_dtype=None):
         """pingpang / sinput: compile()'s isPingpang / isSinput (code/compiler.py:475-510) for the
         fusion search; the reference's start.py passes its command-line flags through.
-        aggregator: the message gathers' reduce function, "ADD" / "MAX" / "MIN" / "MEAN"
-        (frontend.gen_ops; the gathers' COMP_TYPE, executed by gta_reduce / the scaled aggregate).
+        aggregator: the message gathers' reduce function, "ADD" / "MAX" / "MIN" / "MEAN" / "VAR" /
+        "STD" (frontend.gen_ops; the gathers' COMP_TYPE, executed by gta_reduce / the scaled
+        aggregate / gta_reduce_multi), or for PNA a tuple such as ("MEAN", "MAX", "MIN", "STD"):
+        sibling gathers of the same messages, filled by one gta_reduce_multi launch.  The fusion
+        search returns some 3e5 candidate partitions for such a graph at Cora's size, so a tuple
+        aggregator skips it and takes _default_partition() unless op_array is passed.
         stable_softmax: run() evaluates the layer's softmax chains overflow-safe, exp(s - row max)
         (Executor.softmax_shift); off, the default, is the unshifted path.
         gather_dtype: None (the default: nothing changes) or torch.bfloat16 -- run() stores the node
@@ -32,12 +36,19 @@ class Layer:
             raise ValueError(f"gather_dtype: None, torch.float32 or torch.bfloat16, not {gather_dtype}")
         self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
         self.network, self.layer, self.reorder = network, layer, reorder
-        self.aggregator = aggregator
+        multi = isinstance(aggregator, (tuple, list))
+        self.aggregator = tuple(aggregator) if multi else aggregator
         self.stable_softmax = bool(stable_softmax)
         self.graph = graph
         self.records = frontend.gen_ops(network, layer, graph.n_rows, graph.nnz, feature, reorder, heads, aggregator)
-        self.sem = Semantics.for_network(network, reorder)
+        self.sem = Semantics.for_network(network, reorder, clones=frontend.pna_clones(len(aggregator)) if multi else None)
         self.opgraph = ir.OpGraph(self.records, self.sem.inputs)
+        if op_array is None and multi:
+            self.metadata = metadata if metadata is not None else tiles.metadata(
+                graph, start=tile_start or 64, end=min(graph.n_rows, 4096))
+            self.candidates = []
+            op_array = self._default_partition()
+            tile_size_list = [[self.metadata[0][0], 1] for _ in op_array]
         if op_array is None:
             if metadata is None:
                 # tile sizes 64..4096 rows: the 2 MiB buffer rules out larger row tiles

@@ -28,6 +28,28 @@ def is_sum_gather(G):
     return G.type == "gather" and G.order == "R" and G.comp == "ADD"
 
 
+MULTI_COMPS = ("MEAN", "MAX", "MIN", "VAR", "STD")  # what one gta_reduce_multi launch can fill
+
+
+def sibling_gathers(g):
+    """[(gather ops, in op order)] for every group of two or more gathers that read the same
+    producer op with the same ORDER and whose COMP_TYPEs are distinct members of MULTI_COMPS (a PNA
+    layer's aggregators over the same edge messages): one multi-reducer launch fills them all.  A
+    producer that also feeds a gather of that ORDER with any other COMP_TYPE (ADD: the sum has its
+    own fusions) gives no group for that ORDER."""
+    by_site = {}
+    for G in g.ops:
+        ins = g.inputs[G.idx]
+        if G.type == "gather" and len(ins) == 1 and ins[0].kind == "op":
+            by_site.setdefault((ins[0].op, G.order), []).append(G)
+    found = []
+    for _, gs in sorted(by_site.items()):
+        comps = [G.comp for G in gs]
+        if len(gs) >= 2 and all(c in MULTI_COMPS for c in comps) and len(set(comps)) == len(comps):
+            found.append(tuple(G.idx for G in gs))
+    return found
+
+
 def one_scatter(g, P):
     """The one scatter among applyedge P's inputs, or None (none, or several)."""
     sc = [i for i in op_inputs(g, P.idx) if g.ops[i].type == "scatter"]

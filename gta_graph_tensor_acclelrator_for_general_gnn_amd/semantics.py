@@ -40,9 +40,21 @@ class Semantics:
         self.default_sf = default_sf
 
     @classmethod
-    def for_network(cls, network, reorder=False):
+    def for_network(cls, network, reorder=False, clones=None):
+        """clones: None, or {op of an expanded graph: the table's op it is a copy of}
+        (frontend.pna_clones): a copy resolves as its original does; ops at or past the first copy
+        that are copies of nothing take the defaults."""
         t = TABLE.get((network, "trans" if reorder else "original"), {})
-        return cls(t.get("sf"), t.get("bin"), t.get("inputs"))
+        if not clones:
+            return cls(t.get("sf"), t.get("bin"), t.get("inputs"))
+        first = min(clones)
+
+        def moved(d):
+            kept = {i: v for i, v in (d or {}).items() if i < first}
+            kept.update({c: d[o] for c, o in clones.items() if o in (d or {})})
+            return kept
+
+        return cls(moved(t.get("sf")), moved(t.get("bin")), moved(t.get("inputs")))
 
     def sf_of(self, op):
         return self.sf.get(op.idx, self.default_sf)

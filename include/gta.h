@@ -54,7 +54,8 @@ extern "C" {
                               gta_gat_aggregate_blocked_shifted; no existing signature changes);
                               15 (additive): bf16 gathered tables in the blocked forms (gta_aggregate_blocked_x,
                               gta_gat_aggregate_blocked_x; no existing signature changes);
-                              15 (additive): gta_reduce_blocked (column-blocked gather MAX / MIN) */
+                              15 (additive): gta_reduce_blocked (column-blocked gather MAX / MIN);
+                              15 (additive): gta_reduce_multi (MEAN / MAX / MIN / VAR / STD in one pass) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -227,6 +228,42 @@ enum { GTA_RED_ADD = 0, GTA_RED_MAX = 1, GTA_RED_MIN = 2 };
 int gta_reduce(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
                int x_mode, const void* x, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy,
                const void* plan, int64_t plan_chunk, void* workspace, void* stream);
+
+/* ---- K2'' multi-reducer (ABI 15, additive): PNA's aggregators in one pass ---
+ * One walk over each row's edges fills every requested output of MEAN, MAX, MIN, VAR and STD
+ * (which: a non-empty set of GTA_MR_* bits).  ys and ldys are HOST arrays, read during the call,
+ * with one entry per set bit of which, in bit order: ys[k] is [n_rows, F] fp32 with row stride
+ * ldys[k] >= F, so the outputs may be column blocks of one [n_rows, K*F] table (PNA's concat).
+ * idx, x_mode and x_dtype follow gta_reduce (SRC / DST / EDGE; bf16 for SRC / DST, widened exactly).
+ *  - MAX / MIN are gta_reduce's: NaN propagates, every element is bitwise one of its inputs
+ *    (+0 / -0 apart), independent of plan and kernel form.
+ *  - The moments are taken about a shift k(i, c): the operand value at the row's first edge (CSR
+ *    position indptr[i]).  With d the degree, s1 = sum (x - k) and s2 = sum (x - k)^2 in fp32 in
+ *    edge order:  MEAN = k + s1/d;  VAR = max(s2/d - (s1/d)^2, 0), the population variance;
+ *    STD = sqrt(VAR + std_eps).  The sums hold the spread, not the mean, so VAR keeps its digits
+ *    where the unshifted E[x^2] - E[x]^2 has none left (|mean| >> std).  (Rows narrower than a
+ *    wavefront are walked several edges at a time, each slot adding its own edges in order; the
+ *    slots depend on F and the operands' alignment only, never on x_dtype or on which outputs are
+ *    requested, so a bf16 table gives bitwise the fp32 call on its widened rows, two calls are
+ *    bitwise equal, and an output does not change with the others that are requested.)
+ *  - A row without edges gets 0.0f in every output (STD included), decided from its degree.
+ *  - NaN in a (row, column) makes every output of that element NaN.
+ *  - +-inf in a (row, column) makes its MEAN, VAR and STD NaN (inf - inf appears; so does a sum of
+ *    squares past fp32's range); MAX / MIN still follow gta_reduce.  gta_aggregate's MEAN
+ *    (row_scale = 1/deg) is another computation and keeps its own values.
+ * plan: gta_aggregate_plan_build's.  A row split by the plan uses the same k in all its items (each
+ * reads the row's first edge); the items' s1 / s2 are summed, and their extrema folded, in item
+ * order by a second small kernel: deterministic, no atomics.  workspace: at least
+ * gta_aggregate_workspace_bytes(n_rows, nnz, plan_chunk, P * F) bytes, P the planes of partials
+ * the call stores: 2 if which has any of MEAN / VAR / STD, plus 2 if it has MAX or MIN.
+ * Errors, all before any device work: which == 0 or unknown bits, bad x_mode / x_dtype, NULL ys /
+ * ldys / ys[k] or ldys[k] < F: GTA_ERR_ARG; bf16 with x_mode EDGE: GTA_ERR_UNSUPPORTED.
+ * nnz == 0: every output all zero, x and indices never read (may be NULL). */
+enum { GTA_MR_MEAN = 1, GTA_MR_MAX = 2, GTA_MR_MIN = 4, GTA_MR_VAR = 8, GTA_MR_STD = 16 };
+int gta_reduce_multi(int which, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
+                     int x_mode, const void* x, int64_t ldx, int64_t F, int x_dtype,
+                     float* const* ys, const int64_t* ldys, float std_eps,
+                     const void* plan, int64_t plan_chunk, void* workspace, void* stream);
 
 /* ABI 7: the aggregate with a self term, y[i, :] = self_scale[0] * x_self[i, :] + row_scale[i] *
  * sum_{e in row i} w(e) x[idx(e), :] (no accumulate).  x_self has x's dtype and F columns (ld_self
