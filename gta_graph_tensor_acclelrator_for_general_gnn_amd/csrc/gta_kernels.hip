@@ -4730,10 +4730,12 @@ struct AggArgs {
   ExprArgs ex;                                           // gta_aggregate_expr's operands (XM_EX*)
 };
 
+// One wave per row, kWavesPerBlock rows per block (rows: or a bound on the work items of a plan)
+inline dim3 row_grid(int64_t n_rows) { return dim3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock)); }
+
 template <int LPE, int VW, int NV, int XM, int WM, typename TX, int URX = 0>
 void launch_agg(const AggArgs& a, int64_t n_items_bound, hipStream_t s) {
-  const int64_t blocks = (n_items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
-  k_aggregate<LPE, VW, NV, XM, WM, TX, URX><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(
+  k_aggregate<LPE, VW, NV, XM, WM, TX, URX><<<row_grid(n_items_bound), dim3(kBlock), 0, s>>>(
       a.indptr, a.indices, a.n_rows, a.plan, a.use_plan, a.chunk, a.x_is_row, static_cast<const TX*>(a.x), a.ldx, a.F,
       a.w, a.ldw, a.gsz, a.row_scale, a.y, a.ldy, a.accumulate, a.partial, static_cast<const TX*>(a.xs), a.ldxs,
       a.self_scale, a.y_bf16, a.ex);
@@ -5101,7 +5103,7 @@ int64_t gather_args(AggArgs& a, const char* who, const int64_t* indptr, const in
 template <class Launch>
 bool launch_combine(int64_t nnz, int64_t plan_chunk, Launch launch) {
   const int64_t sb = (nnz + plan_chunk - 1) / plan_chunk;  // >= number of split rows
-  if (sb > 0) launch(dim3(static_cast<unsigned>((sb + kWavesPerBlock - 1) / kWavesPerBlock)));
+  if (sb > 0) launch(row_grid(sb));
   return sb > 0;
 }
 
@@ -5185,8 +5187,7 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
   const bool lean_shape = !bf && !y_bf16 && tuning().agg_lean && lpe == kWave && nv == 1 && F == kWave * vw && xm == XM_IDX &&
                           !a.x_is_row && wm != WM_FULL && wm != WM_EDGE1 && (wm == WM_NONE || gl == 4 || gl == 8 || gl == 16);
   if (lean_shape) {
-    const int64_t blocks = (bound + kWavesPerBlock - 1) / kWavesPerBlock;
-    const dim3 grid(static_cast<unsigned>(blocks)), blk(kBlock);
+    const dim3 grid = row_grid(bound), blk(kBlock);
 #define GTA_LEAN(VW_, GL_)                                                                                   \
   k_agg_lean<VW_, GL_><<<grid, blk, 0, s>>>(a.indptr, a.indices, a.n_rows, a.plan, a.use_plan, a.chunk, \
                                             static_cast<const float*>(a.x), a.ldx, a.F, a.w, a.ldw, a.row_scale, \
@@ -5206,8 +5207,7 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
   // lpe == kWave alone also holds for 33..63 lanes (F = 66..126 at VW 2, 132..252 at VW 4), whose
   // idle lanes would load and store past column F: those widths take k_aggregate's XM_EX* form
   if (!ok && ex && tuning().expr_lean && lpe == kWave && nv == 1 && (vw == 2 || vw == 4) && F == kWave * vw) {
-    const int64_t blocks = (bound + kWavesPerBlock - 1) / kWavesPerBlock;
-    const dim3 grid(static_cast<unsigned>(blocks)), blk(kBlock);
+    const dim3 grid = row_grid(bound), blk(kBlock);
 #define GTA_EXPR(VW_, XM_)                                                                                   \
   k_agg_expr<VW_, XM_><<<grid, blk, 0, s>>>(a.indptr, a.indices, a.n_rows, a.plan, a.use_plan, a.chunk, a.ex, a.y, \
                                           a.ldy, a.partial, a.F)
@@ -5242,46 +5242,74 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
   return GTA_OK;
 }
 
-// host-side dispatch of k_reduce (gta_reduce MAX / MIN): aggregate_impl's choice of LPE / VW / NV
+// ---- host side of the row reducers (gta_reduce MAX / MIN here; gta_reduce_multi after with_bools) ----
+
+// The checks both entry points make, in two parts: reduce_multi_impl checks its output arrays between
+// them.  First the sizes, x_mode, x_dtype and what the kernels cannot take; 0 or fail()'s code
+int reduce_check_call(const std::string& who, int64_t n_rows, int64_t nnz, int x_mode, int64_t F, int x_dtype) {
+  if (n_rows < 0 || nnz < 0 || F <= 0) return fail(GTA_ERR_ARG, who + ": bad sizes");
+  if (x_mode != GTA_IDX_EDGE && x_mode != GTA_IDX_SRC && x_mode != GTA_IDX_DST)
+    return fail(GTA_ERR_ARG, who + ": bad x_mode");
+  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, who + ": x_dtype must be F32 or BF16");
+  if (x_dtype == GTA_BF16 && x_mode == GTA_IDX_EDGE)
+    return fail(GTA_ERR_UNSUPPORTED, who + ": bf16 rows are gathered by index (SRC / DST)");
+  if (F > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, who + ": F too large");
+  return GTA_OK;
+}
+
+// Then, with rows to write, the pointers and row strides (y: the output, or the first of several).
+// With no edges, x and indices are never read (may be NULL) and every row gets 0: x becomes y, any
+// valid address
+int reduce_check_operand(const std::string& who, const int64_t* indptr, const int32_t* indices, int64_t nnz, int x_mode,
+                         const void*& x, int64_t& ldx, int64_t F, const float* y, int64_t ldy) {
+  if (!indptr || !y || (nnz > 0 && !x) || ldy < F || (nnz > 0 && ldx < F)) return fail(GTA_ERR_ARG, who + ": bad arguments");
+  if (x_mode == GTA_IDX_SRC && !indices && nnz > 0) return fail(GTA_ERR_ARG, who + ": x_mode SRC needs indices");
+  if (nnz == 0) { x = y; ldx = ldy; }
+  return GTA_OK;
+}
+
+// The reducers' ladder over a GatherShape: fn(LPE, VW, NV, XM as integral constants, TX{}).  bf16 rows
+// are gathered by index only (false: no such kernel), fp32 rows by edge or by index; the 16-B bf16
+// form (g.vw8) exists for indexed bf16 rows alone
+template <class Fn>
+bool dispatch_xm(int xm, bool bf, Fn fn) {
+  if (bf && xm != XM_IDX) return false;
+  if (bf) fn(IC<XM_IDX>{}, uint16_t{});
+  else if (xm == XM_EDGE) fn(IC<XM_EDGE>{}, float{});
+  else fn(IC<XM_IDX>{}, float{});
+  return true;
+}
+
+template <class Fn>
+bool dispatch_gather(const GatherShape& g, int xm, bool bf, Fn fn) {
+  if (g.vw8) {
+    return dispatch_lpe<8>(g.lpe, 1, [&](auto V, auto L, auto N) {
+      fn(L, V, N, IC<XM_IDX>{}, uint16_t{});
+      return true;
+    });
+  }
+  return dispatch_vw(g.vw, g.lpe, g.nv, [&](auto V, auto L, auto N) {
+    return dispatch_xm(xm, bf, [&](auto X, auto tx) { fn(L, V, N, X, tx); });
+  });
+}
+
 template <int LPE, int VW, int NV, int XM, typename TX>
 void launch_red(const AggArgs& a, uint32_t sbit, int64_t n_items_bound, hipStream_t s) {
-  const int64_t blocks = (n_items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
-  k_reduce<LPE, VW, NV, XM, TX><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(
+  k_reduce<LPE, VW, NV, XM, TX><<<row_grid(n_items_bound), dim3(kBlock), 0, s>>>(
       a.indptr, a.indices, a.n_rows, a.plan, a.use_plan, a.x_is_row, static_cast<const TX*>(a.x), a.ldx, a.F, sbit,
       a.y, a.ldy, a.partial);
 }
 
-template <int LPE, int VW, int NV>
-bool dispatch_red_x(int xm, bool bf, const AggArgs& a, uint32_t sbit, int64_t nb, hipStream_t s) {
-  if (bf) {  // bf16 rows are gathered by index only
-    if (xm != XM_IDX) return false;
-    launch_red<LPE, VW, NV, XM_IDX, uint16_t>(a, sbit, nb, s);
-  } else if (xm == XM_EDGE) {
-    launch_red<LPE, VW, NV, XM_EDGE, float>(a, sbit, nb, s);
-  } else {
-    launch_red<LPE, VW, NV, XM_IDX, float>(a, sbit, nb, s);
-  }
-  return true;
-}
-
+// gta_reduce MAX / MIN: aggregate_impl's choice of LPE / VW / NV
 int reduce_impl(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
                 const void* x, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy, const void* plan,
                 int64_t plan_chunk, void* workspace, void* stream) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
-  if (n_rows < 0 || nnz < 0 || F <= 0) return fail(GTA_ERR_ARG, "reduce: bad sizes");
-  if (x_mode != GTA_IDX_EDGE && x_mode != GTA_IDX_SRC && x_mode != GTA_IDX_DST)
-    return fail(GTA_ERR_ARG, "reduce: bad x_mode");
-  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, "reduce: x_dtype must be F32 or BF16");
+  if (const int rc = reduce_check_call("reduce", n_rows, nnz, x_mode, F, x_dtype)) return rc;
+  if (n_rows == 0) return GTA_OK;
+  if (const int rc = reduce_check_operand("reduce", indptr, indices, nnz, x_mode, x, ldx, F, y, ldy)) return rc;
   const bool bf = x_dtype == GTA_BF16;
   const int xe = bf ? 2 : 4;  // bytes per x element
-  if (bf && x_mode == GTA_IDX_EDGE)
-    return fail(GTA_ERR_UNSUPPORTED, "reduce: bf16 rows are gathered by index (SRC / DST)");
-  if (F > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, "reduce: F too large");
-  if (n_rows == 0) return GTA_OK;
-  // with no edges, x and indices are never read (may be NULL); every row gets 0
-  if (!indptr || !y || (nnz > 0 && !x) || ldy < F || (nnz > 0 && ldx < F)) return fail(GTA_ERR_ARG, "reduce: bad arguments");
-  if (x_mode == GTA_IDX_SRC && !indices && nnz > 0) return fail(GTA_ERR_ARG, "reduce: x_mode SRC needs indices");
-  if (nnz == 0) { x = y; ldx = ldy; }  // any valid address: no row has an edge to read
   const int xm = (x_mode == GTA_IDX_EDGE) ? XM_EDGE : XM_IDX;
   auto ok_vw = [&](int vw) {
     return !(F % vw || ldx % vw || ldy % vw || !aligned(x, xe * vw) || !aligned(y, 4 * vw));
@@ -5295,15 +5323,9 @@ int reduce_impl(int red, const int64_t* indptr, const int32_t* indices, int64_t 
   if (bound < 0) return static_cast<int>(bound);
   const uint32_t sbit = red == GTA_RED_MIN ? 0x80000000u : 0u;
   hipStream_t s = S(stream);
-  bool ok;
-  if (g.vw8) {
-    ok = dispatch_lpe<8>(g.lpe, 1, [&](auto, auto L, auto) {
-      launch_red<L(), 8, 1, XM_IDX, uint16_t>(a, sbit, bound, s);
-      return true;
-    });
-  } else {
-    ok = dispatch_vw(g.vw, g.lpe, g.nv, [&](auto V, auto L, auto N) { return dispatch_red_x<L(), V(), N()>(xm, bf, a, sbit, bound, s); });
-  }
+  const bool ok = dispatch_gather(g, xm, bf, [&](auto L, auto V, auto N, auto X, auto tx) {
+    launch_red<L(), V(), N(), X(), decltype(tx)>(a, sbit, bound, s);
+  });
   if (!ok) return fail(GTA_ERR_UNSUPPORTED, "reduce: no kernel variant");
   GTA_LAUNCHED("k_reduce");
   const bool combined = plan && launch_combine(nnz, plan_chunk, [&](dim3 grid) {
@@ -5385,9 +5407,6 @@ void dispatch_heads(int64_t heads, Fn fn) {
   }
 }
 
-// One wave per row, kWavesPerBlock rows per block
-inline dim3 row_grid(int64_t n_rows) { return dim3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock)); }
-
 // May a K3 kernel move vw floats per lane?  out and each full-width operand (g == 1) vw-float aligned,
 // a head-broadcast operand with vw output columns in one head.  ops._flat_aligned mirrors this in Python.
 bool vec_ok(int vw, const float* a, int64_t lda, int ga, const float* b, int64_t ldb, int gb, const float* out,
@@ -5408,32 +5427,16 @@ int check_heads(const char* who, int64_t heads, int sf, bool need_exp, int64_t l
   return GTA_OK;
 }
 
-// host-side dispatch of k_reduce_multi (gta_reduce_multi): reduce_impl's shape, ladder and combine
-// pattern, specialised on which accumulator families the call needs
+// gta_reduce_multi: reduce_impl's path, specialised on which accumulator families the call needs
 template <int LPE, int VW, int NV, int XM, typename TX>
 void launch_multi(bool mom, bool ext, const AggArgs& a, const MultiOut& out, float eps, int64_t pstride,
                   int64_t n_items_bound, hipStream_t s) {
-  const int64_t blocks = (n_items_bound + kWavesPerBlock - 1) / kWavesPerBlock;
   with_bools([&](auto M, auto E) {
     if constexpr ((M() || E()) && !(M() && VW == 8))  // (the 16-B bf16 pieces carry the extrema only)
-      k_reduce_multi<LPE, VW, NV, XM, M(), E(), TX><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(
+      k_reduce_multi<LPE, VW, NV, XM, M(), E(), TX><<<row_grid(n_items_bound), dim3(kBlock), 0, s>>>(
           a.indptr, a.indices, a.n_rows, a.plan, a.use_plan, a.x_is_row, static_cast<const TX*>(a.x), a.ldx, a.F, out,
           eps, a.partial, pstride);
   }, mom, ext);
-}
-
-template <int LPE, int VW, int NV>
-bool dispatch_multi_x(int xm, bool bf, bool mom, bool ext, const AggArgs& a, const MultiOut& out, float eps,
-                      int64_t pstride, int64_t nb, hipStream_t s) {
-  if (bf) {  // bf16 rows are gathered by index only
-    if (xm != XM_IDX) return false;
-    launch_multi<LPE, VW, NV, XM_IDX, uint16_t>(mom, ext, a, out, eps, pstride, nb, s);
-  } else if (xm == XM_EDGE) {
-    launch_multi<LPE, VW, NV, XM_EDGE, float>(mom, ext, a, out, eps, pstride, nb, s);
-  } else {
-    launch_multi<LPE, VW, NV, XM_IDX, float>(mom, ext, a, out, eps, pstride, nb, s);
-  }
-  return true;
 }
 
 int reduce_multi_impl(int which, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
@@ -5443,15 +5446,7 @@ int reduce_multi_impl(int which, const int64_t* indptr, const int32_t* indices, 
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
   constexpr int kAll = GTA_MR_MEAN | GTA_MR_MAX | GTA_MR_MIN | GTA_MR_VAR | GTA_MR_STD;
   if (which == 0 || (which & ~kAll)) return fail(GTA_ERR_ARG, "reduce_multi: which must be a non-empty set of GTA_MR_* bits");
-  if (n_rows < 0 || nnz < 0 || F <= 0) return fail(GTA_ERR_ARG, "reduce_multi: bad sizes");
-  if (x_mode != GTA_IDX_EDGE && x_mode != GTA_IDX_SRC && x_mode != GTA_IDX_DST)
-    return fail(GTA_ERR_ARG, "reduce_multi: bad x_mode");
-  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, "reduce_multi: x_dtype must be F32 or BF16");
-  const bool bf = x_dtype == GTA_BF16;
-  const int xe = bf ? 2 : 4;  // bytes per x element
-  if (bf && x_mode == GTA_IDX_EDGE)
-    return fail(GTA_ERR_UNSUPPORTED, "reduce_multi: bf16 rows are gathered by index (SRC / DST)");
-  if (F > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, "reduce_multi: F too large");
+  if (const int rc = reduce_check_call("reduce_multi", n_rows, nnz, x_mode, F, x_dtype)) return rc;
   if (!ys || !ldys) return fail(GTA_ERR_ARG, "reduce_multi: ys / ldys is NULL");
   MultiOut out{};
   float* y0 = nullptr;
@@ -5464,10 +5459,9 @@ int reduce_multi_impl(int which, const int64_t* indptr, const int32_t* indices, 
     ++k;
   }
   if (n_rows == 0) return GTA_OK;
-  // with no edges, x and indices are never read (may be NULL); every row gets 0
-  if (!indptr || (nnz > 0 && !x) || (nnz > 0 && ldx < F)) return fail(GTA_ERR_ARG, "reduce_multi: bad arguments");
-  if (x_mode == GTA_IDX_SRC && !indices && nnz > 0) return fail(GTA_ERR_ARG, "reduce_multi: x_mode SRC needs indices");
-  if (nnz == 0) { x = y0; ldx = ldy0; }  // any valid address: no row has an edge to read
+  if (const int rc = reduce_check_operand("reduce_multi", indptr, indices, nnz, x_mode, x, ldx, F, y0, ldy0)) return rc;
+  const bool bf = x_dtype == GTA_BF16;
+  const int xe = bf ? 2 : 4;  // bytes per x element
   const int xm = (x_mode == GTA_IDX_EDGE) ? XM_EDGE : XM_IDX;
   auto outs_ok = [&](int vw, int bytes) {  // every requested output's rows aligned to vw floats / bytes
     for (int b = 0; b < MR_N; ++b)
@@ -5488,17 +5482,9 @@ int reduce_multi_impl(int which, const int64_t* indptr, const int32_t* indices, 
   if (bound < 0) return static_cast<int>(bound);
   const int64_t pstride = bound * F;  // one plane of partials: gta_aggregate_workspace_bytes(..., F)
   hipStream_t s = S(stream);
-  bool ok;
-  if (g.vw8) {
-    ok = dispatch_lpe<8>(g.lpe, 1, [&](auto, auto L, auto) {
-      launch_multi<L(), 8, 1, XM_IDX, uint16_t>(mom, ext, a, out, std_eps, pstride, bound, s);
-      return true;
-    });
-  } else {
-    ok = dispatch_vw(g.vw, g.lpe, g.nv, [&](auto V, auto L, auto N) {
-      return dispatch_multi_x<L(), V(), N()>(xm, bf, mom, ext, a, out, std_eps, pstride, bound, s);
-    });
-  }
+  const bool ok = dispatch_gather(g, xm, bf, [&](auto L, auto V, auto N, auto X, auto tx) {
+    launch_multi<L(), V(), N(), X(), decltype(tx)>(mom, ext, a, out, std_eps, pstride, bound, s);
+  });
   if (!ok) return fail(GTA_ERR_UNSUPPORTED, "reduce_multi: no kernel variant");
   GTA_LAUNCHED("k_reduce_multi");
   const bool combined = plan && launch_combine(nnz, plan_chunk, [&](dim3 grid) {
