@@ -66,6 +66,9 @@ SIGNATURES = {
                                        _i64, _i32, _vp, _i64, _i64, _vp, _vp]),
     "gta_reduce_blocked": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64,
                                   _vp, _vp]),
+    "gta_reduce_multi_blocked_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i32]),
+    "gta_reduce_multi_blocked": (_i32, [_i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, ctypes.c_float,
+                                        _vp, _i64, _i64, _vp, _vp]),
     "gta_gat_aggregate_blocked_x": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64,
                                            _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "gta_apply_edge_flat": (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _vp, _i64,

@@ -71,6 +71,9 @@ def parser():
     p.add_argument("--gather-dtype", choices=["f32", "bf16"], default="f32",
                    help="storage type of the node tables the column-blocked aggregates gather (bf16: rounded "
                         "once, sums in fp32; f32: as they are)")
+    p.add_argument("--multi-reduce-blocked", action="store_true",
+                   help="sibling gathers and lone VAR / STD gathers of a node table beyond L2 take one column-blocked "
+                        "multi-reducer launch (off: the row-chunked launch; the moments' last bits differ)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--reps", type=int, default=3, help="runs per layer; the fastest is reported")
     p.add_argument("--model-edges", type=int, default=1 << 20,
@@ -100,6 +103,8 @@ def run(args, device, log=print):
                   stable_softmax=getattr(args, "stable_softmax", False))
         if getattr(args, "gather_dtype", "f32") == "bf16":
             kw["gather_dtype"] = torch.bfloat16
+        if getattr(args, "multi_reduce_blocked", False):
+            kw["multi_reduce_blocked"] = True
         lay = None
         for k, (op_array, tile_size_list) in enumerate(c[:2] for c in cands):
             try:

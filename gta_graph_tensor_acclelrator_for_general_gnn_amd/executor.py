@@ -189,7 +189,7 @@ MAX_MATERIALIZE_BYTES = 96 << 30  # refuse to materialise a single edge tensor l
 
 class Executor:
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, dist=None,
-                 softmax_shift=None, gather_dtype=None, multi_reduce=True):
+                 softmax_shift=None, gather_dtype=None, multi_reduce=True, multi_reduce_blocked=False):
         self.g = opgraph
         # dist (distributed.Comm): node tensors are this rank's row block; gathers are
         # reduce-scattered to it and dst-side scatters all-gather it (distributed.py)
@@ -229,6 +229,12 @@ class Executor:
         #   of them is evaluated -- the messages are read once; False: one launch per gather (A/B).
         #   MAX / MIN are the single launches' values, the moments within their rounding bound.
         self.multi_reduce = bool(multi_reduce)
+        #   multi_reduce_blocked: False (the default: every route, trace and bit is unchanged), or True --
+        #   a sibling group, or a lone VAR / STD gather, whose operand passes reduce_blocked's gate (a
+        #   virtual scatter of a source table beyond L2: _multi_blocks) takes ONE ops.reduce_multi_blocked
+        #   launch whatever the group's size, over the cast table under gather_dtype.  Opt-in because the
+        #   blocked grouping of the sums moves the bits of MEAN / VAR / STD (within their bound).
+        self.multi_reduce_blocked = bool(multi_reduce_blocked)
         self.std_eps = 1e-5  # STD = sqrt(VAR + std_eps)
         self.siblings = {i: grp for grp in rewrites.sibling_gathers(opgraph) for i in grp}
         self._multi_vals = {}  # sibling gather -> its value from the group's launch, until it is evaluated
@@ -929,8 +935,15 @@ class Executor:
         E, F = self.graph.nnz, t.shape[1]
         group = self.siblings.get(op.idx) if self.multi_reduce else None
         if group is not None and self._multi_wanted(group, v, t, g, col):
-            return self._eval_multi(op, group, g, t, mode, n_out, index=col or scat, row_es=t.element_size() if col else 4)
+            return self._eval_multi(op, group, g, t, mode, n_out, index=col or scat, row_es=t.element_size() if col else 4,
+                                    blocks=self._multi_blocks(tuple(self.g.ops[i].comp for i in group), v, t, g, col))
         if op.comp in MOMENTS:  # one member: the same kernel family, the moment accumulators only
+            B = self._multi_blocks((op.comp,), v, t, g, col)
+            if B:
+                tb = t if col else self._gather_cast(t)
+                y, = ops.reduce_multi_blocked(g, tb, (op.comp,), blocks=B, std_eps=self.std_eps)
+                self._count(self._gather_bytes(E, n_out, F, tb.element_size()))
+                return NodeT(y)
             y, = ops.reduce_multi(g, t, (op.comp,), mode, plan=self._plan(), std_eps=self.std_eps)
             self._count(self._gather_bytes(E, n_out, F, t.element_size() if col else 4, index=col or scat))
             return NodeT(y)
@@ -963,8 +976,12 @@ class Executor:
         return NodeT(y)
 
     def _would_block(self, comp, v, t, g, col):
-        """_eval_reduce's column-blocked gate for one gather of COMP_TYPE comp reading v (table t)."""
-        if not (self.reduce_blocked and isinstance(v, Scat)) or comp in MOMENTS:
+        """_eval_reduce's column-blocked gate for one gather of COMP_TYPE comp reading v (table t): for
+        VAR / STD the gate of the one-member ops.reduce_multi_blocked launch that _eval_reduce would
+        send (_multi_blocks with that member's two planes; closed without multi_reduce_blocked)."""
+        if comp in MOMENTS:
+            return bool(self._multi_blocks((comp,), v, t, g, col))
+        if not (self.reduce_blocked and isinstance(v, Scat)):
             return False
         if not col and v.mode == "src" and (comp != "MEAN" or self.gather_dtype == torch.bfloat16):
             return bool(self._blocked_blocks(t, "src", 0))
@@ -972,19 +989,42 @@ class Executor:
             return bool(self._blocked_blocks(t, "src", 0, g))
         return False
 
+    def _multi_blocks(self, reds, v, t, g, col):
+        """Column blocks of ops.reduce_multi_blocked for the reducers reds reading v (table t), or 0:
+        under multi_reduce_blocked, _eval_reduce's two blocked cases and size gate, with the
+        edges-per-block floor of reduce_multi_planes(reds) partial rows per item."""
+        if not (self.multi_reduce_blocked and self.reduce_blocked and isinstance(v, Scat)):
+            return 0
+        if v.mode != ("dst" if col else "src"):
+            return 0
+        return self._blocked_blocks(t, "src", 0, g if col else None, planes=ops.reduce_multi_planes(reds))
+
     def _multi_wanted(self, group, v, t, g, col):
-        """The group launch runs row-chunked only.  Where every member would take the column-blocked
-        form on its own, the one pass replaces len(group) cheaper ones: from MULTI_MIN_BLOCKED members."""
+        """Without multi_reduce_blocked the group launch runs row-chunked only: where every member would
+        take the column-blocked form on its own, the one pass replaces len(group) cheaper ones, from
+        MULTI_MIN_BLOCKED members.  With it, a group whose operand passes the gate for the group's planes
+        (_multi_blocks) takes the one blocked launch whatever its size.  Under blocked_blocks "auto" that
+        gate's edges-per-block floor grows with the planes, so it can close for a pair (four planes)
+        while each member's own gate (one or two planes, _would_block) stays open: such a pair runs as
+        its two blocked launches, as a pair of blocked gathers does without the flag."""
         if len(group) >= MULTI_MIN_BLOCKED:
+            return True
+        if self._multi_blocks(tuple(self.g.ops[i].comp for i in group), v, t, g, col):
             return True
         return not all(self._would_block(self.g.ops[i].comp, v, t, g, col) for i in group)
 
-    def _eval_multi(self, op, group, g, t, mode, n_out, index, row_es):
+    def _eval_multi(self, op, group, g, t, mode, n_out, index, row_es, blocks=0):
         """Every gather of op's sibling group from ONE ops.reduce_multi launch (op: the first of them
-        to be evaluated); the others find their value in _multi_vals.  Bytes: the operand read once,
-        one output per member."""
+        to be evaluated) -- with blocks (_multi_blocks), ONE ops.reduce_multi_blocked launch over the
+        table as the blocked kernels gather it; the others find their value in _multi_vals.  Bytes:
+        the operand read once, one output per member."""
         reds = tuple(self.g.ops[i].comp for i in group)
-        ys = ops.reduce_multi(g, t, reds, mode, plan=self._plan(), std_eps=self.std_eps)
+        if blocks:
+            t = t if self.g.ops[group[0]].order == "C" else self._gather_cast(t)
+            ys = ops.reduce_multi_blocked(g, t, reds, blocks=blocks, std_eps=self.std_eps)
+            index, row_es = True, t.element_size()
+        else:
+            ys = ops.reduce_multi(g, t, reds, mode, plan=self._plan(), std_eps=self.std_eps)
         E, F = self.graph.nnz, t.shape[1]
         self._count(self._gather_bytes(E, n_out, F, row_es, index=index) + (len(group) - 1) * n_out * 4 * F)
         for i, y in zip(group, ys):
@@ -1054,10 +1094,10 @@ class Executor:
             return ops.aggregate_blocked(g, xt, wt, out=acc, accumulate=acc is not None, blocks=B)
         return ops.aggregate(g, xt, mode, wt, out=acc, accumulate=acc is not None, plan=self._plan())
 
-    def _blocked_blocks(self, xt, mode, heads, graph=None):
+    def _blocked_blocks(self, xt, mode, heads, graph=None, planes=1):
         """Column blocks of the blocked aggregate for this gathered table, or 0 for the row-chunked
         form: a source table of at least blocked_min_table_bytes (its own element size) of a dtype
-        and width the blocked kernels take."""
+        and width the blocked kernels take.  planes: partial rows per item (BlockedPlan.auto_blocks)."""
         g = self.graph if graph is None else graph
         # the table as it will be gathered: with gather_dtype bf16, _spmm rounds an fp32 table of the
         # layer's own CSR (not of the ORDER-C views) to bf16, and a bf16 table is taken as it is; with
@@ -1071,7 +1111,8 @@ class Executor:
             return 0
         B = self.blocked_blocks
         if B == "auto":
-            B = ops.BlockedPlan.auto_blocks(g, xt.shape[1], es)
+            extra = {"planes": planes} if planes != 1 else {}  # (the one-plane request is the call it always was)
+            B = ops.BlockedPlan.auto_blocks(g, xt.shape[1], es, **extra)
             B = B if B >= 4 else 0
         return B if B and g.blocked_plan(B).sorted else 0
 
@@ -1492,14 +1533,15 @@ def set_auto_graph(flag):
         clear_auto_graphs()
 
 
-def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=None, gather_dtype=None):
+def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=None, gather_dtype=None,
+                multi_reduce_blocked=False):
     """-> a GraphedRun to replay for this call, or None (run eagerly)."""
     if ops.Tuning.attached(torch.cuda.current_stream(graph.device)):
         return None  # a knob set on this stream: every call reads it (gta.h), so no cached graph
     refs = (opgraph, stream, graph, semantics)
     shifted = SOFTMAX_SHIFT if softmax_shift is None else bool(softmax_shift)
     gdt = None if gather_dtype == torch.float32 else gather_dtype
-    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt), id(tensors), ops.knob_state())
+    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt, bool(multi_reduce_blocked)), id(tensors), ops.knob_state())
     ent = _AUTO_FAST.get(fkey)
     if ent is not None and not (ent.src is tensors and all(a is b for a, b in zip(ent.refs, refs)) and
                                 len(tensors) == len(ent.tensors) and
@@ -1533,7 +1575,7 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_
         before = torch.cuda.memory_reserved(graph.device)
         try:
             ent.run = GraphedRun(opgraph, stream, graph, ent.tensors, semantics, plan_chunk, warmup=1,
-                                 softmax_shift=shifted, gather_dtype=gdt)
+                                 softmax_shift=shifted, gather_dtype=gdt, multi_reduce_blocked=multi_reduce_blocked)
         except Exception:  # something in this stream is not capturable: stay eager for this key
             ent.failed = True
             torch.cuda.synchronize(graph.device)
@@ -1562,14 +1604,16 @@ def _evict_pools(keep):
 
 
 def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, sync=True, trace=False,
-               softmax_shift=None, gather_dtype=None):
+               softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False):
     """softmax_shift: Executor.softmax_shift for this call (None: the module's SOFTMAX_SHIFT).
-    gather_dtype: Executor.gather_dtype for this call (None: tables are gathered as they are)."""
+    gather_dtype: Executor.gather_dtype for this call (None: tables are gathered as they are).
+    multi_reduce_blocked: Executor.multi_reduce_blocked for this call (False: today's routes)."""
     dev = graph.device
     if not AUTO_GRAPH and _AUTO:
         clear_auto_graphs()
     if AUTO_GRAPH and not trace and dev.type == "cuda" and graph.nnz <= AUTO_GRAPH_MAX_EDGES:
-        gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift, gather_dtype)
+        gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift, gather_dtype,
+                         multi_reduce_blocked)
         if gr is not None:
             if sync:
                 torch.cuda.synchronize(dev)
@@ -1580,7 +1624,7 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
             ex = gr.executor
             return ExecResult(ex.values, outputs, time.perf_counter() - t0, ex.alg_bytes, ex.launches), ex
     ex = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
-                  gather_dtype=gather_dtype)
+                  gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked)
     ex.trace = trace
     sync = sync and dev.type == "cuda"
     if sync:
@@ -1768,7 +1812,7 @@ class GraphedRun:
     place (its version moved) is re-concatenated / re-transposed into them before the next replay."""
 
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, warmup=2,
-                 softmax_shift=None, gather_dtype=None):
+                 softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False):
         if graph.device.type != "cuda":
             raise RuntimeError("GraphedRun captures device launches: the graph must be on a HIP device")
         self.tensors = tensors
@@ -1777,7 +1821,7 @@ class GraphedRun:
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
-                         gather_dtype=gather_dtype).run()
+                         gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked).run()
         torch.cuda.current_stream(graph.device).wait_stream(side)
         torch.cuda.synchronize(graph.device)
         self.cuda_graph = torch.cuda.CUDAGraph()
@@ -1786,7 +1830,8 @@ class GraphedRun:
         try:
             with torch.cuda.graph(self.cuda_graph):
                 self.executor = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk,
-                                         softmax_shift=softmax_shift, gather_dtype=gather_dtype)
+                                         softmax_shift=softmax_shift, gather_dtype=gather_dtype,
+                                         multi_reduce_blocked=multi_reduce_blocked)
                 self.outputs = self.executor.run()
         finally:
             taken, ops._CAPTURED_WT[:] = list(ops._CAPTURED_WT), []

@@ -11,6 +11,8 @@ One function per ISA op / fused pattern of the GTA stream:
                (PNA's aggregators; the moments about the row's first value)  -> gta_reduce_multi
   reduce_blocked  the same MAX / MIN gather of a node table, column-blocked for tables beyond L2
                (the blocked aggregate's plan and slab rows)                 -> gta_reduce_blocked
+  reduce_multi_blocked  reduce_multi's outputs over that plan: one blocked walk for MEAN / MAX /
+               MIN / VAR / STD of a node table beyond L2                    -> gta_reduce_multi_blocked
   apply_edge   applyedge ADD/MUL/SF (genGraphOP.py:36, 55-60)            -> gta_apply_edge
   aggregate_expr  a tree of applyedge ops -> gather ADD, fused (DGN, PNA)   -> gta_aggregate_expr
   apply_node   applynode ADD/MUL/SF (genGraphOP.py:62, 94-95, 103-108)     -> gta_apply_node
@@ -456,6 +458,17 @@ class BlockedPlan:
             self._ws[F] = torch.empty(int(nb), dtype=torch.uint8, device=self.graph.device)
         return self._ws[F]
 
+    def workspace_multi(self, F, reds):
+        """Partial rows of the column-blocked multi-reducer over reds ([items, P * F] fp32,
+        P = reduce_multi_planes(reds)); one buffer per (F, P)."""
+        key = ("multi", F, reduce_multi_planes(reds))
+        if key not in self._ws:
+            nb = check(_L().gta_reduce_multi_blocked_workspace_bytes(self.graph.n_rows, self.graph.nnz, self.blocks, F,
+                                                                     self.item_edges, sum(_MR_BITS[r] for r in reds)),
+                       "reduce_multi_blocked_workspace_bytes")
+            self._ws[key] = torch.empty(int(nb), dtype=torch.uint8, device=self.graph.device)
+        return self._ws[key]
+
     def workspace_att(self, F, heads):
         """Partial rows of the fused attention aggregate ([items, F + heads padded to 4])."""
         key = ("att", F, heads)
@@ -478,19 +491,22 @@ class BlockedPlan:
     DTYPES = (torch.float32, torch.bfloat16)  # gathered-table dtypes of the blocked kernels
 
     @staticmethod
-    def auto_blocks(graph, F, elem=4):
+    def auto_blocks(graph, F, elem=4, *, planes=1):
         """Column blocks for a gathered table of graph.n_cols x F elements of `elem` bytes: slices
         of ~6 MB (measured optima with the lean half-wave kernel: B = 20 for the 119 MB Reddit
         table, B = 10 for the 60 MB column half of a 2-D grid tile; profiles/r01_blocks_rowmerge_sweep.json,
         r01_shard_b_sweep.json), capped so a row keeps >= 24 edges per block on average (each
         (block, row) item pays a start-up and a partial row written and re-read).
+        planes: the partial rows an item writes and the reduce re-reads -- 1 for the aggregates and
+        reduce_blocked, reduce_multi_planes(reds) for reduce_multi_blocked, whose per-item cost is
+        that many rows: the edges-per-block floor scales with it (24 * planes).
         Below 4 the single-pass row-chunk kernel is the better choice.
         This is the REQUEST: the count a caller passes as `blocks`.  The default plan of such a
         request may be built over finer blocks that light rows merge back (BlockedPlan.resolve,
         knobs seg_fine_pct / seg_row_edges; DESIGN §3.1 has the sweep that set them)."""
         table_mb = graph.n_cols * F * elem / 1e6
         avg_deg = graph.nnz / max(1, graph.n_rows)
-        return int(max(1, min(24, round(table_mb / 6.0), avg_deg // 24)))
+        return int(max(1, min(24, round(table_mb / 6.0), avg_deg // (24 * int(planes)))))
 
     @staticmethod
     def supports(F, heads, dtype=torch.float32):
@@ -594,6 +610,60 @@ def reduce_blocked(graph, x, red="MAX", out=None, plan=None, blocks=32):
                                   _ptr(plan.buf), plan.blocks, plan.item_edges, _ptr(plan.workspace(F)),
                                   _stream(x.device)), "reduce_blocked")
     return out
+
+
+def reduce_multi_blocked(graph, x, reds, outs=None, out=None, plan=None, blocks=32, std_eps=1e-5):
+    """reduce_multi(graph, x, reds, "src") computed column block by column block
+    (gta_reduce_multi_blocked), for a gathered table beyond L2: every item of the blocked plan walks
+    its edges once for all the requested reducers and an ordered pass combines each row's items.
+    MAX / MIN are reduce()'s values for any plan.  The moments keep reduce_multi's definition (the
+    shift k is the operand at the row's first edge, one k for all items of the row) but sum s1 / s2
+    per item and then in item order, so they are deterministic and within the same bound, not
+    bitwise reduce_multi's.  A bf16 x is bitwise the call on x.float(); an output does not depend on
+    which others are requested.  reds, outs, out, std_eps: as reduce_multi; x, plan, blocks and the
+    sorted-rows requirement: as reduce_blocked (graph may be a CSC.view("dst"))."""
+    reds = tuple(reds)
+    if not reds or len(set(reds)) != len(reds) or any(r not in _MR_BITS for r in reds):
+        raise ValueError(f"reduce_multi_blocked: reds must be distinct names from {MULTI_REDS} (got {reds!r})")
+    if outs is not None and out is not None:
+        raise ValueError("reduce_multi_blocked: give outs or out, not both")
+    _need_gpu(x, out, graph.indptr, *(outs or ()))
+    if x.dtype not in BlockedPlan.DTYPES:
+        raise ValueError(f"reduce_multi_blocked: unsupported dtype={x.dtype}")
+    F, K = x.shape[1], len(reds)
+    if not BlockedPlan.supports(F, 0, x.dtype):
+        raise ValueError(f"reduce_multi_blocked: unsupported F={F}, dtype={x.dtype}")
+    bf = x.dtype == torch.bfloat16
+    ldx = _rows(x, "x", x.dtype)
+    if ldx % (8 if bf else 4) or x.data_ptr() % 16:
+        raise ValueError("reduce_multi_blocked: x needs 16-B aligned rows (ldx % 4 == 0 for fp32, ldx % 8 == 0 for bf16)")
+    if x.shape[0] < graph.n_cols:
+        raise ValueError("x must have n_cols rows")
+    if plan is None:
+        plan = graph.blocked_plan(blocks)
+    if not plan.sorted:
+        raise ValueError("reduce_multi_blocked needs every CSR row's columns sorted")
+    if out is not None:
+        if out.dim() != 2 or out.shape[0] < graph.n_rows or out.shape[1] != K * F:
+            raise ValueError("reduce_multi_blocked: out must be [N, len(reds) * F]")
+        outs = tuple(out[:, k * F:(k + 1) * F] for k in range(K))
+    elif outs is None:
+        outs = tuple(torch.empty(graph.n_rows, F, dtype=torch.float32, device=x.device) for _ in reds)
+    outs = tuple(outs)
+    if len(outs) != K or any(o.shape[0] < graph.n_rows or o.shape[1] != F for o in outs):
+        raise ValueError("reduce_multi_blocked: one [N, F] output per reducer")
+    lds = [_rows(o, "out") for o in outs]
+    if graph.n_rows == 0:
+        return outs
+    order = sorted(range(K), key=lambda k: _MR_BITS[reds[k]])  # the ABI takes them in bit order
+    ys = (ctypes.c_void_p * K)(*(outs[k].data_ptr() for k in order))
+    ldys = (ctypes.c_int64 * K)(*(lds[k] for k in order))
+    which = sum(_MR_BITS[r] for r in reds)
+    check(_L().gta_reduce_multi_blocked(which, _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols,
+                                        graph.nnz, _ptr(x), ldx, F, _lib.GTA_BF16 if bf else _lib.GTA_F32, ys, ldys,
+                                        float(std_eps), _ptr(plan.buf), plan.blocks, plan.item_edges,
+                                        _ptr(plan.workspace_multi(F, reds)), _stream(x.device)), "reduce_multi_blocked")
+    return outs
 
 
 def blocked_ready(graph, blocks):

@@ -19,7 +19,7 @@ class Layer:
 
     def __init__(self, network, layer, graph, feature, reorder=False, heads=16, candidate=0, tile_start=None,
                  op_array=None, tile_size_list=None, metadata=None, pingpang=True, sinput=False, aggregator="ADD",
-                 stable_softmax=False, gather_dtype=None):
+                 stable_softmax=False, gather_dtype=None, multi_reduce_blocked=False):
         """pingpang / sinput: compile()'s isPingpang / isSinput (code/compiler.py:475-510) for the
         fusion search; the reference's start.py passes its command-line flags through.
         aggregator: the message gathers' reduce function, "ADD" / "MAX" / "MIN" / "MEAN" / "VAR" /
@@ -31,7 +31,10 @@ class Layer:
         stable_softmax: run() evaluates the layer's softmax chains overflow-safe, exp(s - row max)
         (Executor.softmax_shift); off, the default, is the unshifted path.
         gather_dtype: None (the default: nothing changes) or torch.bfloat16 -- run() stores the node
-        tables its column-blocked aggregates gather as bf16 (Executor.gather_dtype)."""
+        tables its column-blocked aggregates gather as bf16 (Executor.gather_dtype).
+        multi_reduce_blocked: False (the default: nothing changes) or True -- run() sends sibling
+        gathers and lone VAR / STD gathers of a source table beyond L2 through one column-blocked
+        gta_reduce_multi_blocked launch (Executor.multi_reduce_blocked)."""
         if gather_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError(f"gather_dtype: None, torch.float32 or torch.bfloat16, not {gather_dtype}")
         self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
@@ -39,6 +42,7 @@ class Layer:
         multi = isinstance(aggregator, (tuple, list))
         self.aggregator = tuple(aggregator) if multi else aggregator
         self.stable_softmax = bool(stable_softmax)
+        self.multi_reduce_blocked = bool(multi_reduce_blocked)
         self.graph = graph
         self.records = frontend.gen_ops(network, layer, graph.n_rows, graph.nnz, feature, reorder, heads, aggregator)
         self.sem = Semantics.for_network(network, reorder, clones=frontend.pna_clones(len(aggregator)) if multi else None)
@@ -97,6 +101,8 @@ class Layer:
             opts["softmax_shift"] = True
         if self.gather_dtype is not None:
             opts["gather_dtype"] = self.gather_dtype
+        if self.multi_reduce_blocked:
+            opts["multi_reduce_blocked"] = True
         res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync,
                                       **opts)
         if model:

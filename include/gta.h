@@ -55,7 +55,8 @@ extern "C" {
                               15 (additive): bf16 gathered tables in the blocked forms (gta_aggregate_blocked_x,
                               gta_gat_aggregate_blocked_x; no existing signature changes);
                               15 (additive): gta_reduce_blocked (column-blocked gather MAX / MIN);
-                              15 (additive): gta_reduce_multi (MEAN / MAX / MIN / VAR / STD in one pass) */
+                              15 (additive): gta_reduce_multi (MEAN / MAX / MIN / VAR / STD in one pass);
+                              15 (additive): gta_reduce_multi_blocked (the same, column-blocked) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -404,6 +405,45 @@ int gta_gat_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, i
 int gta_reduce_blocked(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
                        int64_t nnz, const void* x, int64_t ldx, int64_t F, int x_dtype, float* y, int64_t ldy,
                        const void* plan, int64_t blocks, int64_t item_edges, void* workspace, void* stream);
+
+/* ---- K2'' column-blocked multi-reducer (ABI 15, additive): gta_reduce_multi's outputs over
+ * gta_reduce_blocked's plan, for a gathered table beyond L2 ----
+ * which, ys, ldys and std_eps follow gta_reduce_multi (HOST arrays read during the call, one entry
+ * per set GTA_MR_* bit in bit order; the outputs may be column blocks of one [n_rows, K*F] table);
+ * plan, blocks and item_edges follow gta_reduce_blocked (gta_aggregate_blocked_plan_build's plan,
+ * unchanged; rows' columns sorted); x is gathered by source index (GTA_IDX_SRC).  Every plan item
+ * walks its edges once and stores P planes of F partials -- P as in gta_reduce_multi: 2 if which has
+ * any of MEAN / VAR / STD, plus 2 if it has MAX or MIN -- and a second kernel combines each row's
+ * items in the plan's (block, part) order.  workspace: gta_reduce_multi_blocked_workspace_bytes =
+ * P * gta_aggregate_blocked_workspace_bytes.
+ *  - MAX / MIN obey gta_reduce's rules: NaN propagates; every element is bitwise one of its inputs
+ *    (+0 / -0 apart); a row without edges gets 0.0f, decided from its item count; the values equal
+ *    gta_reduce's for any plan, blocks, item_edges and kernel form.
+ *  - The moments are gta_reduce_multi's: the shift k(i, c) is the operand at the row's first edge,
+ *    the same k in every item of the row; s1 = sum (x - k) and s2 = sum (x - k)^2 are summed in fp32
+ *    in each item's edge order, then across the row's items in (block, part) order; MEAN = k + s1/d,
+ *    VAR = max(s2/d - (s1/d)^2, 0), STD = sqrt(VAR + std_eps).  Deterministic, but not bitwise
+ *    gta_reduce_multi's: the sums are grouped differently.  A row of identical values has VAR
+ *    exactly 0.  NaN and +-inf as in gta_reduce_multi (a NaN makes every output of its element NaN,
+ *    a +-inf its MEAN, VAR and STD); a row without edges gets 0.0f in every output.
+ *  - x_dtype GTA_F32 or GTA_BF16, widened exactly (ldx in bf16 elements): a bf16 call is bitwise the
+ *    fp32 call on the widened table.
+ *  - An output does not change with which other outputs are requested; two calls are bitwise equal.
+ * Shapes: gta_reduce_blocked's -- F in {64, 128, 256} on the multi-item forms only, fp32 x 16-B
+ * aligned with ldx % 4 == 0, bf16 x 16-B aligned with ldx % 8 == 0, anything else
+ * GTA_ERR_UNSUPPORTED; F = 128 takes the 32-bit row addressing under gta_aggregate_blocked_x's
+ * guards (knob seg_lean).  Outputs whose rows are not all aligned to F / 64 floats are written
+ * element by element (the same values).
+ * GTA_ERR_ARG, before any device work: which == 0 or unknown bits, a bad x_dtype, blocks outside
+ * 1..63, item_edges < 1, NULL ys / ldys / ys[k] or ldys[k] < F, NULL indptr / plan, NULL x /
+ * indices / workspace with nnz > 0.
+ * n_rows == 0 returns GTA_OK; nnz == 0: every output all zero, x and indices never read. */
+int64_t gta_reduce_multi_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, int64_t blocks, int64_t F,
+                                                 int64_t item_edges, int which);
+int gta_reduce_multi_blocked(int which, const int64_t* indptr, const int32_t* indices, int64_t n_rows,
+                             int64_t n_cols, int64_t nnz, const void* x, int64_t ldx, int64_t F, int x_dtype,
+                             float* const* ys, const int64_t* ldys, float std_eps,
+                             const void* plan, int64_t blocks, int64_t item_edges, void* workspace, void* stream);
 
 /* ---- CSC view of the CSR (ABI 11) -----------------------------------------
  * The edges ordered by SOURCE column, for the ISA gather / scatter with DIRECTION src
