@@ -26,6 +26,7 @@ import torch
 
 from . import compiler, executor, frontend, graph as G, pipeline, tiles, workloads
 
+GATHER_DTYPES = {"f32": None, "bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # --gather-dtype
 FEATURES = {"cora": 1433, "citeseer": 3703, "pubmed": 500, "flickr": 500, "reddit": 602,
             "products": 100}  # genGraphOP.py:178-195 (cora / pubmed / citeseer / reddit); configs.py (flickr / products)
 
@@ -68,9 +69,10 @@ def parser():
                         "takes a comma list, e.g. MEAN,MAX,MIN,STD: every aggregator over the same messages, one launch")
     p.add_argument("--stable-softmax", action="store_true",
                    help="overflow-safe attention softmax: exp(score - row max) (GAT; off: the unshifted kernels)")
-    p.add_argument("--gather-dtype", choices=["f32", "bf16"], default="f32",
-                   help="storage type of the node tables the column-blocked aggregates gather (bf16: rounded "
-                        "once, sums in fp32; f32: as they are)")
+    p.add_argument("--gather-dtype", choices=list(GATHER_DTYPES), default="f32",
+                   help="storage type of the node tables the column-blocked aggregates gather (bf16 / fp8 = OCP e4m3: "
+                        "rounded once, sums in fp32; fp8 is not scaled: values below 2^-10 round to 0, |x| > 448 "
+                        "saturates; f32: as they are)")
     p.add_argument("--multi-reduce-blocked", action="store_true",
                    help="sibling gathers and lone VAR / STD gathers of a node table beyond L2 take one column-blocked "
                         "multi-reducer launch (off: the row-chunked launch; the moments' last bits differ)")
@@ -101,8 +103,8 @@ def run(args, device, log=print):
         kw = dict(reorder=args.isReorder, heads=args.heads, metadata=meta, pingpang=args.isPingpang,
                   sinput=args.isSinput, aggregator=getattr(args, "aggregator", "ADD"),
                   stable_softmax=getattr(args, "stable_softmax", False))
-        if getattr(args, "gather_dtype", "f32") == "bf16":
-            kw["gather_dtype"] = torch.bfloat16
+        if GATHER_DTYPES[getattr(args, "gather_dtype", "f32")] is not None:
+            kw["gather_dtype"] = GATHER_DTYPES[args.gather_dtype]
         if getattr(args, "multi_reduce_blocked", False):
             kw["multi_reduce_blocked"] = True
         lay = None

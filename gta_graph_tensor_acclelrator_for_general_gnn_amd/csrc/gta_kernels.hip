@@ -1278,18 +1278,24 @@ struct AttArgs {
   const float* shift = nullptr;  // SH: [n_rows, H] contiguous row maxima of g(a + b) (k_softmax_shift)
 };
 
-// BF forms of the blocked item kernels (gta_aggregate_blocked_x / gta_gat_aggregate_blocked_x with
-// GTA_BF16): x points at bf16 rows (read as uint16_t; ldx / row_bytes in its units) and four
-// consecutive columns of a gathered row stay two raw dwords (Row4<true>) until the fma, where each
-// element widens exactly (bits << 16).  Same lanes, columns, edge order and fma chain as the fp32
-// form: bitwise its result on the widened table.
-template <bool BF> struct Row4 {
+// Element types of the blocked item kernels' gathered rows (gta_aggregate_blocked_x /
+// gta_gat_aggregate_blocked_x): x points at fp32, bf16 (GTA_BF16) or OCP e4m3 (GTA_FP8) rows and a
+// row piece -- four consecutive columns -- stays raw in registers (Row4<ET>: a float4, two dwords,
+// one dword) until the fma, where each element widens exactly (bf16: bits << 16; fp8:
+// v_cvt_pk_f32_fp8, two elements per instruction).  Same columns, edge order and fma chain as the
+// fp32 form: bitwise its result on the widened table.  A bool BF converts to E_F32 / E_BF16.
+enum { E_F32 = 0, E_BF16 = 1, E_FP8 = 2 };
+template <int ET> struct Row4 {
   typedef float4 type;
   static __device__ __forceinline__ float4 zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 };
-template <> struct Row4<true> {
+template <> struct Row4<E_BF16> {
   typedef uint2 type;
   static __device__ __forceinline__ uint2 zero() { return make_uint2(0u, 0u); }
+};
+template <> struct Row4<E_FP8> {
+  typedef uint32_t type;
+  static __device__ __forceinline__ uint32_t zero() { return 0u; }
 };
 // keeps a row piece's registers written where the source writes them (no code)
 __device__ __forceinline__ void row4_pin(float4& r) { asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w)); }
@@ -1298,6 +1304,15 @@ __device__ __forceinline__ float4 row4_f32(const float4& r) { return r; }
 __device__ __forceinline__ float4 row4_f32(const uint2& r) {
   return make_float4(__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
                      __uint_as_float(r.y & 0xffff0000u));
+}
+// four e4m3 codes of one dword, byte k = column k (0x00 / 0x80 -> +-0, so Row4<E_FP8>::zero() is four zeros)
+__device__ __forceinline__ float4 row4_f32(const uint32_t& r) {
+  const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(r), false);
+  const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(r), true);
+  return make_float4(lo[0], lo[1], hi[0], hi[1]);
+}
+__device__ __forceinline__ float load_elem(const uint8_t* p) {  // one e4m3 code (beside the bf16 load_elem)
+  return __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(*p), false)[0];
 }
 
 // ---- what the blocked item kernels share: item decode, row loads, slab-row store, the fold ----
@@ -1344,11 +1359,24 @@ __device__ __forceinline__ T lean_at(const char* base, int src, uint32_t row_byt
 }
 
 // Generic addressing (64-bit): the lane's NQ pieces of row src from column col.  bf16: one 8-B load
-// (NQ = 1) or 16-B loads split into two pieces each (NQ = 4).
-template <bool BF, int NQ>
+// (NQ = 1) or 16-B loads split into two pieces each (NQ = 4).  fp8: the lane's 4 NQ bytes in one load
+// (NQ = 1, 2, 4: dword, dwordx2, dwordx4); ldx counts bytes.
+template <int ET, int NQ>
 __device__ __forceinline__ void row_load(const float* x, int64_t ldx, int src, int col,
-                                         typename Row4<BF>::type (&xv)[NQ]) {
-  if constexpr (BF) {
+                                         typename Row4<ET>::type (&xv)[NQ]) {
+  if constexpr (ET == E_FP8) {
+    static_assert(NQ == 1 || NQ == 2 || NQ == 4, "4, 8 or 16 bytes per lane");
+    const uint8_t* pb = reinterpret_cast<const uint8_t*>(x) + static_cast<int64_t>(src) * ldx + col;
+    if constexpr (NQ == 4) {
+      const uint4 t = *reinterpret_cast<const uint4*>(pb);
+      xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
+    } else if constexpr (NQ == 2) {
+      const uint2 t = *reinterpret_cast<const uint2*>(pb);
+      xv[0] = t.x; xv[1] = t.y;
+    } else {
+      xv[0] = *reinterpret_cast<const uint32_t*>(pb);
+    }
+  } else if constexpr (ET == E_BF16) {
     const uint16_t* pb = reinterpret_cast<const uint16_t*>(x) + static_cast<int64_t>(src) * ldx + col;
     if constexpr (NQ % 2 == 0) {
 #pragma unroll
@@ -1387,27 +1415,28 @@ __device__ __forceinline__ void slab_store(float* o, const float (&acc)[VW]) {
 // identity -- as the bit pattern that the flip turns into -inf (RedIdle), so the fold needs no
 // per-edge select and masked lanes issue no loads.  Slab rows hold partials in the MAX domain: the
 // ordered reduce folds them with sbit 0 and flips the result back.
-template <bool BF> struct RedIdle {  // the row piece whose every element flips to -inf
+template <int ET> struct RedIdle {  // the row piece whose every element flips to -inf (e4m3 has none: no fp8 form)
   static __device__ __forceinline__ float4 make(uint32_t sbit) {
     const float v = __uint_as_float(0xff800000u ^ sbit);
     return make_float4(v, v, v, v);
   }
 };
-template <> struct RedIdle<true> {
+template <> struct RedIdle<E_BF16> {
   static __device__ __forceinline__ uint2 make(uint32_t sbit) {
     const uint32_t h = (0xff800000u ^ sbit) >> 16, v = h | (h << 16);
     return make_uint2(v, v);
   }
 };
-template <bool BF> struct FoldSum {
+template <int ET> struct FoldSum {
   static constexpr float kInit = 0.f;
-  __device__ __forceinline__ typename Row4<BF>::type idle() const { return Row4<BF>::zero(); }
+  __device__ __forceinline__ typename Row4<ET>::type idle() const { return Row4<ET>::zero(); }
   __device__ __forceinline__ float combine(float acc, float x) const { return acc + x; }
 };
-template <bool BF> struct FoldMax {
+template <int ET> struct FoldMax {
+  static_assert(ET != E_FP8, "no -inf in e4m3: MAX / MIN take no fp8 rows");
   uint32_t sbit;
   static constexpr float kInit = -__builtin_inff();
-  __device__ __forceinline__ typename Row4<BF>::type idle() const { return RedIdle<BF>::make(sbit); }
+  __device__ __forceinline__ typename Row4<ET>::type idle() const { return RedIdle<ET>::make(sbit); }
   __device__ __forceinline__ float combine(float acc, float x) const { return red_max(acc, red_flip(x, sbit)); }
 };
 
@@ -1415,13 +1444,13 @@ template <bool BF> struct FoldMax {
 // indices arrive in one coalesced load (the next chunk's behind it) and are broadcast lane by lane;
 // per step U rows are gathered, lanes of a finished item masked off, and folded.  An item without
 // edges, or a lane group past n_items, stores nothing.  NT as in k_agg_seg4.
-template <int VW, int U, int G, int NT, bool BF, class Fold>
+template <int VW, int U, int G, int NT, int ET, class Fold>
 __device__ __forceinline__ void seg4_walk(const int32_t* indices, const int64_t* n_items_p,
                                           const float* x, int64_t ldx, float* slabs,
                                           const SegItem* items, Fold fold) {
   constexpr int F = G * VW;
   constexpr int NQ = VW / 4;
-  typedef typename Row4<BF>::type XR;
+  typedef typename Row4<ET>::type XR;
   const int lane = threadIdx.x & (kWave - 1);
   const int l16 = lane & (G - 1);
   const ItemSlot d = item_decode<G>(n_items_p, items, lane);
@@ -1445,7 +1474,7 @@ __device__ __forceinline__ void seg4_walk(const int32_t* indices, const int64_t*
       for (int u = 0; u < U; ++u) {
         const int src = bcastG<G>(idxv, s + u);
         if (c + s + u < len) {
-          row_load<BF, NQ>(x, ldx, src, col, xv[u]);
+          row_load<ET, NQ>(x, ldx, src, col, xv[u]);
         } else {
 #pragma unroll
           for (int q = 0; q < NQ; ++q) xv[u][q] = idle;
@@ -1468,17 +1497,18 @@ __device__ __forceinline__ void seg4_walk(const int32_t* indices, const int64_t*
 }
 
 template <int VW, int U, bool WEIGHTED, int NT = 0, bool ATT = false, int SFC = -1, int G = 16, bool SH = false,
-          bool BF = false>
+          int ET = E_F32>
 // NT bit 0: non-temporal index/weight loads, bit 1: slab stores; SFC >= 0: the ATT special function
 // fixed at compile time (-1: att.sf at run time); G = lanes per item (16: four items per wave,
 // 32: two items per wave -- one 512-B row per half-wave instruction at F = 128); SH: the ATT
-// weight is the shifted one, expf(g(a + b) - att.shift[row, h])
+// weight is the shifted one, expf(g(a + b) - att.shift[row, h]); ET: the rows' element type (E_FP8: a
+// lane holds VW bytes, G = 16 at every width -- VW = 4, 8, 16 for F = 64, 128, 256)
 __global__ void __launch_bounds__(kBlock)
 k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
            int64_t ldx, const float* __restrict__ w, int64_t ldw, int lph, float* __restrict__ slabs,
            const SegItem* __restrict__ items, AttArgs att = AttArgs{}) {
   if constexpr (!WEIGHTED && !ATT) {  // the plain sum: the shared walk
-    seg4_walk<VW, U, G, NT, BF>(indices, n_items_p, x, ldx, slabs, items, FoldSum<BF>{});
+    seg4_walk<VW, U, G, NT, ET>(indices, n_items_p, x, ldx, slabs, items, FoldSum<ET>{});
     return;
   }
   constexpr int F = G * VW;
@@ -1507,14 +1537,14 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
 #pragma unroll
     for (int s = 0; s < G; s += U) {
       if (c + s >= maxlen) break;
-      typename Row4<BF>::type xv[U][NQ];
+      typename Row4<ET>::type xv[U][NQ];
       float wu[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int src = bcastG<G>(idxv, s + u);
         const bool ok = c + s + u < len;
         if (ok) {
-          row_load<BF, NQ>(x, ldx, src, col, xv[u]);
+          row_load<ET, NQ>(x, ldx, src, col, xv[u]);
           if (ATT) {
             const float sv = arow + att.b[static_cast<int64_t>(src) * att.ldb + head];
             if (SH) wu[u] = (SFC >= 0) ? sf_shift(SFC, sv, mrow) : sf_shift(att.sf, sv, mrow);
@@ -1526,7 +1556,7 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
           }
         } else {
 #pragma unroll
-          for (int q = 0; q < NQ; ++q) xv[u][q] = Row4<BF>::zero();
+          for (int q = 0; q < NQ; ++q) xv[u][q] = Row4<ET>::zero();
           wu[u] = 0.f;
         }
       }
@@ -1862,6 +1892,106 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
     else wc += static_cast<int64_t>(G) * ldw;
   }
   if (len > 0) slab_store<(NT & 2) != 0>(slabs + k * F + l32 * 4, acc);
+}
+
+// Lean quarter-wave form for F = 128 e4m3 rows (GTA_FP8; the metric shape among them): FOUR items per
+// wave, 16 lanes x 8 B each, so one wave instruction gathers four whole 128-B rows -- the lines per
+// instruction of the bf16 half-wave form with twice the edges.  A lane keeps its 8 columns of a row
+// as two raw dwords until the fold, where v_cvt_pk_f32_fp8 widens two at a time.
+//  * rows by lean_at: the uniform base x plus src * row_bytes + 8 l16 (the host checks lean32_ok);
+//  * a chunk is 16 edges -- one coalesced index load per item, the next chunk's behind it, bcast16;
+//  * a step is 8 edges, unmasked when every non-empty item of the wave still holds 8 (wave-uniform,
+//    against the shortest non-empty item; a lane group without an item then gathers row 0 and the
+//    first edges' weights, both inside the tables, and stores nothing), masked otherwise;
+//  * MODE 0: unweighted (acc + x).  MODE 1: one weight per edge, riding with the indices as W1's do.
+//    MODE 2: 8 head weights -- a head is a PAIR of lanes; lane p of the pair loads its head's weights
+//    of the step's edges 2j + p and takes those of 2j + (p ^ 1) from its neighbour by a DPP quad
+//    permutation: 8 dword loads per lane per 16 edges against the generic form's 16.
+// Each column keeps k_agg_seg4's chain (one accumulator per item, fmaf in edge order, +0 from an
+// idle slot): bitwise equal to k_agg_seg4<8, 8, ., ., ., ., 16, ., E_FP8>, hence to the fp32 call on
+// the widened table.  Index loads and slab stores are non-temporal.  Opt-in (knob seg_lean = 2): as
+// measured it loses to the generic form in all three modes (DESIGN 3.13 has the figures).
+__device__ __forceinline__ float quad_swap1(float v) {  // lane l ^ 1 (quad_perm [1, 0, 3, 2])
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(kBlock)
+k_agg_q16f8(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const void* __restrict__ x,
+            uint32_t row_bytes, const float* __restrict__ w, int64_t ldw, float* __restrict__ slabs,
+            const SegItem* __restrict__ items) {
+  constexpr int G = 16, F = 128, U = 8;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int l16 = lane & (G - 1);
+  const ItemSlot d = item_decode<G>(n_items_p, items, lane);
+  const int len = d.it.len, maxlen = d.maxlen;
+  if (maxlen == 0) return;
+  int mn = len > 0 ? len : INT32_MAX;  // the shortest non-empty item of the wave
+  mn = min(mn, __shfl_xor(mn, 16));
+  mn = min(mn, __shfl_xor(mn, 32));
+  const int minlen = __builtin_amdgcn_readfirstlane(mn);
+  const uint32_t colb = static_cast<uint32_t>(l16) * 8u;
+  const char* xb = static_cast<const char*>(x);
+  const int h = l16 >> 1, p = l16 & 1;
+  const int ldw32 = static_cast<int>(ldw);  // host: ldw < 2^24
+  // chunk cursors: advanced once per 16 edges, so no per-edge 64-bit offsets are live
+  const int32_t* ic = indices + d.it.beg;
+  const float* wc = MODE ? w + d.it.beg * ldw + (MODE == 2 ? h : 0) : nullptr;
+  auto ldi = [&](const int32_t* q) { return __builtin_nontemporal_load(q); };
+  auto row = [&](int src) { return lean_at<uint2>(xb, src, row_bytes, colb); };
+  float acc[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) acc[t] = 0.f;
+  int idxv = (l16 < len) ? ldi(ic + l16) : 0;
+  float wv = (MODE == 1 && l16 < len) ? wc[l16 * ldw32] : 0.f;  // MODE 1: this chunk's weights, lane = edge
+  for (int c = 0; c < maxlen; c += G) {
+    const int idxn = (c + G + l16 < len) ? ldi(ic + G + l16) : 0;
+    const float wvn = (MODE == 1 && c + G + l16 < len) ? wc[(G + l16) * ldw32] : 0.f;
+#pragma unroll
+    for (int s = 0; s < G; s += U) {
+      if (c + s >= maxlen) break;
+      uint2 xv[U];
+      float wu[U];
+      const int rem = len - c - s;  // edges of this item left at this step (may be <= 0)
+      const bool full = c + s + U <= minlen;  // every non-empty item holds the whole step: no masks
+      if (full) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) xv[u] = row(bcast16(idxv, s + u));
+      } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int src = bcast16(idxv, s + u);
+          if (u < rem) xv[u] = row(src);
+          else xv[u] = make_uint2(0u, 0u);
+        }
+      }
+      if constexpr (MODE == 1) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) wu[u] = __int_as_float(bcast16(__float_as_int(wv), s + u));  // past len: +0
+      } else if constexpr (MODE == 2) {
+#pragma unroll
+        for (int j = 0; j < U / 2; ++j) {
+          const int e = s + 2 * j + p;  // the lane's edge of pair j, counted from the chunk
+          const float mine = (full || 2 * j + p < rem) ? wc[e * ldw32] : 0.f;
+          const float other = quad_swap1(mine);
+          wu[2 * j] = p ? other : mine;
+          wu[2 * j + 1] = p ? mine : other;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float4 lo = row4_f32(xv[u].x), hi = row4_f32(xv[u].y);
+        const float xf[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+        for (int t = 0; t < 8; ++t) acc[t] = MODE ? fmaf(wu[u], xf[t], acc[t]) : acc[t] + xf[t];
+      }
+    }
+    idxv = idxn;
+    if (MODE == 1) wv = wvn;
+    ic += G;
+    if (MODE) wc += static_cast<int64_t>(G) * ldw;
+  }
+  if (len > 0) slab_store<true>(slabs + d.k * F + l16 * 8, acc);
 }
 
 // Column-blocked MAX / MIN (gta_reduce_blocked): the unweighted walks with FoldMax.  Item k's slab
@@ -5091,7 +5221,8 @@ struct Tuning {
   int force_lpe = 0;       // k_aggregate lanes per edge (0 = automatic; 32 = float4 lanes at F = 128)
   int force_vw = 0;        // k_aggregate floats per lane (0 = widest aligned)
   int agg_lean = 1;        // k_agg_lean for F = 64*VW SpMM shapes (0: k_aggregate, the form of other shapes)
-  int seg_lean = 1;        // k_agg_h32 (32-bit row offsets, unmasked full steps, DPP weights) for F = 128
+  int seg_lean = 1;        // k_agg_h32 (32-bit row offsets, unmasked full steps, DPP weights) for F = 128; 2: also
+                           // the lean fp8 kernel k_agg_q16f8 (0 / 1: e4m3 rows take the generic quarter-wave form)
   int seg_lean_w1 = 1;     // k_agg_h32 with one weight per edge (H = 1: GCN, GraphSAGE-mean) for F = 128
   int seg_pf = 0;          // k_agg_h32pf: alpha / index lines pre-fetched into L2 by scalar loads (1: 64-B granules,
                            // 1 step ahead; 2: 128 B, 1 step; 3: 64 B, 2 steps; 4: 128 B, 2 steps; 5: as 1, held to
@@ -5880,8 +6011,10 @@ int64_t gta_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, int64
 
 // gta_aggregate_blocked (who "aggregate_blocked", GTA_F32) and gta_aggregate_blocked_x: one argument
 // check, one dispatch; the fp32 launches are the instantiations they always were.  bf16 rows
-// (xv, ldx in bf16 elements) take the multi-item forms only -- the <..., BF = true> twins of the
+// (xv, ldx in bf16 elements) take the multi-item forms only -- the <..., E_BF16> twins of the
 // fp32 launches; the scalar-prefetch form (seg_pf) has no bf16 twin and is not selected for them.
+// e4m3 rows (GTA_FP8: ldx in bytes) take the quarter-wave forms at every width,
+// k_agg_seg4<F/16, 8, ., ., ., ., 16, ., E_FP8>; knob seg_lean = 2: the lean k_agg_q16f8 at F = 128.
 static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr, const int32_t* indices, int64_t n_rows,
                                   int64_t n_cols, int64_t nnz, const void* xv, int64_t ldx, int64_t F, int x_dtype,
                                   const float* w, int64_t ldw, int64_t heads, const float* row_scale, float* y,
@@ -5890,14 +6023,15 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
   if (n_rows < 0 || nnz < 0 || F <= 0 || blocks < 1 || blocks > 63 || item_edges < 1)
     return fail(GTA_ERR_ARG, who + ": bad sizes");
-  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, who + ": x_dtype must be F32 or BF16");
+  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16 && x_dtype != GTA_FP8)
+    return fail(GTA_ERR_ARG, who + ": x_dtype must be F32, BF16 or FP8");
   if (n_rows == 0) return GTA_OK;
   if (!indptr || !xv || !y || !plan) return fail(GTA_ERR_ARG, who + ": bad arguments");
-  const bool bf = x_dtype == GTA_BF16;
+  const bool bf = x_dtype == GTA_BF16, f8 = x_dtype == GTA_FP8;
   const float* x = static_cast<const float*>(xv);  // bf: bf16 rows, read as such by the BF kernels only
   int gl = 0, vw = 0;
   for (int c : {4, 2, 1}) {
-    if (F == static_cast<int64_t>(kWave) * c && (bf || (ldx % c == 0 && aligned(x, 4 * c))) && ldy % c == 0 &&
+    if (F == static_cast<int64_t>(kWave) * c && (bf || f8 || (ldx % c == 0 && aligned(x, 4 * c))) && ldy % c == 0 &&
         aligned(y, 4 * c)) {
       vw = c;
       break;
@@ -5918,22 +6052,46 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
   const int lph = w ? static_cast<int>((F / heads) / vq) : 0;
   // multi-item waves (F = 64 / 256: four 16-lane items; F = 128: two 32-lane items, one 512-B row per
   // half-wave instruction) when rows are 16-B aligned and the heads fit the lanes; else one item per wave
-  const bool quarter = (vq == 4 || vq == 8 || vq == 16) && ldx % (bf ? 8 : 4) == 0 && aligned(x, 16) &&
+  const unsigned xe = f8 ? 1u : (bf ? 2u : 4u);  // bytes per gathered element
+  const bool quarter = (vq == 4 || vq == 8 || vq == 16) && ldx % (16 / xe) == 0 && aligned(x, 16) &&
                        (!w || ((F / heads) % vq == 0 && lph >= 1 && 16 % lph == 0));
   if (bf && !quarter)  // the one-item-per-wave fallback (k_agg_seg2d) has no bf16 twin
     return fail(GTA_ERR_UNSUPPORTED, who + ": bf16 rows need x 16-B aligned, ldx % 8 == 0 and heads that fit the "
                                            "multi-item forms (F/heads a multiple of F/16, lanes per head dividing 16)");
+  if (f8 && !quarter)  // nor an fp8 one
+    return fail(GTA_ERR_UNSUPPORTED, who + ": fp8 rows need x 16-B aligned, ldx % 16 == 0 and heads that fit the "
+                                           "quarter-wave forms (F/heads a multiple of F/16, lanes per head dividing 16)");
   const int phase = tuning().seg_phase;
-  const unsigned xe = bf ? 2u : 4u;  // bytes per gathered element
-  // the generic G-lane form <VW, U, WEIGHTED, NT, no ATT, G, BF>, fp32 and bf16, weighted or not
-  auto seg4 = [&](auto VW, auto U, auto NT, auto G, dim3 grid, int lanes_per_head) {
+  // the generic G-lane form <VW, U, WEIGHTED, NT, no ATT, G, ET>, weighted or not: fp32 and bf16 in one
+  // lane layout, the fp8 shapes (F8: G = 16, VW = F/16 at every width) for e4m3 rows alone
+  auto seg4 = [&](auto VW, auto U, auto NT, auto G, dim3 grid, int lanes_per_head, auto F8) {
     with_bools([&](auto W, auto BF) {
-      k_agg_seg4<VW(), U(), W(), NT(), false, -1, G(), false, BF()><<<grid, c.blk, 0, c.s>>>(
+      constexpr int ET = F8() ? E_FP8 : (BF() ? E_BF16 : E_F32);
+      k_agg_seg4<VW(), U(), W(), NT(), false, -1, G(), false, ET><<<grid, c.blk, 0, c.s>>>(
           indices, c.nit, x, ldx, w, ldw, lanes_per_head, c.slabs, c.its);
     }, w != nullptr, bf);
   };
+  constexpr BC<true> fp8{};
+  constexpr BC<false> wide{};
   if (c.items == 0 || phase == 2) {
     // no edges: no items; the reduce below writes the (empty) rows (phase 2: the reduce only)
+  } else if (f8) {  // quarter-wave items at every width, a lane holds F/16 bytes of the row
+    // the lean F = 128 kernel is opt-in (seg_lean = 2): measured, the generic form beats it in every case
+    // (Reddit 8 heads 2.98 vs 3.42 ms, unweighted 1.78 vs 1.89), so 0 and 1 take the generic form
+    const bool lean = vq == 8 && tuning().seg_lean == 2 && lean32_ok(n_cols, ldx, xe) &&
+                      (!w || ((heads == 8 || heads == 1) && ldw < (int64_t(1) << 24)));
+    if (lean) {
+      const uint32_t rb = static_cast<uint32_t>(ldx);
+      if (!w) k_agg_q16f8<0><<<c.g4, c.blk, 0, c.s>>>(indices, c.nit, xv, rb, w, ldw, c.slabs, c.its);
+      else if (heads == 1) k_agg_q16f8<1><<<c.g4, c.blk, 0, c.s>>>(indices, c.nit, xv, rb, w, ldw, c.slabs, c.its);
+      else k_agg_q16f8<2><<<c.g4, c.blk, 0, c.s>>>(indices, c.nit, xv, rb, w, ldw, c.slabs, c.its);
+      GTA_LAUNCHED("k_agg_q16f8");
+    } else {
+      if (vq == 4) seg4(IC<4>{}, IC<8>{}, IC<0>{}, IC<16>{}, c.g4, lph, fp8);
+      else if (vq == 8) seg4(IC<8>{}, IC<8>{}, IC<2>{}, IC<16>{}, c.g4, lph, fp8);
+      else seg4(IC<16>{}, IC<8>{}, IC<0>{}, IC<16>{}, c.g4, lph, fp8);
+      GTA_LAUNCHED("k_agg_seg4<fp8>");
+    }
   } else if (quarter && vq == 8) {  // F = 128: half-wave items, 32 lanes x float4 (bf16: x 8 B)
     const int lph32 = w ? static_cast<int>((F / heads) / 4) : 0;
     const bool lean = tuning().seg_lean && lean32_ok(n_cols, ldx, xe) &&
@@ -5972,12 +6130,12 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
       else h32(no, IC<2>{}, no, no);
       GTA_LAUNCHED("k_agg_h32");
     } else {
-      seg4(IC<4>{}, IC<8>{}, IC<2>{}, IC<32>{}, c.g2h, lph32);
+      seg4(IC<4>{}, IC<8>{}, IC<2>{}, IC<32>{}, c.g2h, lph32, wide);
       GTA_LAUNCHED("k_agg_seg4<half>");
     }
   } else if (quarter) {  // F = 64 / 256: quarter-wave items
-    if (vq == 4) seg4(IC<4>{}, IC<4>{}, IC<0>{}, IC<16>{}, c.g4, lph);
-    else seg4(IC<16>{}, IC<2>{}, IC<0>{}, IC<16>{}, c.g4, lph);
+    if (vq == 4) seg4(IC<4>{}, IC<4>{}, IC<0>{}, IC<16>{}, c.g4, lph, wide);
+    else seg4(IC<16>{}, IC<2>{}, IC<0>{}, IC<16>{}, c.g4, lph, wide);
     GTA_LAUNCHED("k_agg_seg4");
   } else {
     if (!gl_ok) return fail(GTA_ERR_UNSUPPORTED, gl_msg);
@@ -6181,7 +6339,8 @@ int64_t gta_gat_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, i
 
 // gta_gat_aggregate_blocked (shifted false), gta_gat_aggregate_blocked_shifted and
 // gta_gat_aggregate_blocked_x: one argument check, one dispatch; the fp32 launches are the
-// instantiations they always were, bf16 rows (xv, ldx in bf16 elements) launch their <..., BF = true> twins.
+// instantiations they always were, bf16 rows (xv, ldx in bf16 elements) launch their <..., E_BF16> twins;
+// e4m3 rows (GTA_FP8, ldx in bytes) the generic quarter-wave ATT forms at every width.
 static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64_t* indptr, const int32_t* indices,
                                       int64_t n_rows, int64_t n_cols, int64_t nnz, const void* xv, int64_t ldx,
                                       int64_t F, int x_dtype, const float* a_dst, int64_t lda, const float* b_src, int64_t ldb,
@@ -6192,10 +6351,11 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
   if (n_rows < 0 || nnz < 0 || blocks < 1 || blocks > 63 || heads <= 0 || lda < heads || ldb < heads ||
       item_edges < 1 || sf_out < GTA_SF_NONE || sf_out > GTA_SF_RECIP)
     return fail(GTA_ERR_ARG, std::string(who) + ": bad sizes");
-  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16)
-    return fail(GTA_ERR_ARG, std::string(who) + ": x_dtype must be F32 or BF16");
-  const bool bf = x_dtype == GTA_BF16;
-  const float* x = static_cast<const float*>(xv);  // bf: bf16 rows, read as such by the BF kernels only
+  if (x_dtype != GTA_F32 && x_dtype != GTA_BF16 && x_dtype != GTA_FP8)
+    return fail(GTA_ERR_ARG, std::string(who) + ": x_dtype must be F32, BF16 or FP8");
+  const bool bf = x_dtype == GTA_BF16, f8 = x_dtype == GTA_FP8;
+  const unsigned xe = f8 ? 1u : (bf ? 2u : 4u);  // bytes per gathered element
+  const float* x = static_cast<const float*>(xv);  // bf16 / fp8 rows: read as such by their kernels only
   if (shifted && !shift) return fail(GTA_ERR_ARG, std::string(who) + ": shift is required");
   if (shifted && !sf_is_exp_form(sf))
     return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": sf must be EXP_LEAKY_RELU or EXP");
@@ -6203,10 +6363,10 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
   if (!indptr || !x || !a_dst || !b_src || !y || !plan || (!workspace && nnz > 0))
     return fail(GTA_ERR_ARG, std::string(who) + ": bad arguments");
   const int vq = static_cast<int>(F / 16);
-  if ((F != 64 && F != 128 && F != 256) || F % heads || (F / heads) % vq || ldx % (bf ? 8 : 4) || !aligned(x, 16) ||
+  if ((F != 64 && F != 128 && F != 256) || F % heads || (F / heads) % vq || ldx % (16 / xe) || !aligned(x, 16) ||
       ldy % (F / 64) || !aligned(y, 4 * (F / 64)))
-    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": F in {64,128,256}, 16-B rows (bf16: ldx % 8 == 0), F/heads "
-                                                          "a multiple of F/16");
+    return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": F in {64,128,256}, 16-B rows (bf16: ldx % 8 == 0, fp8: "
+                                                          "ldx % 16 == 0), F/heads a multiple of F/16");
   const int lph = static_cast<int>((F / heads) / vq);
   if (lph < 1 || 16 % lph) return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": lanes per head must divide 16");
   const BlockedCall c(plan, n_rows, nnz, blocks, item_edges, workspace, stream);
@@ -6214,18 +6374,25 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
   int skip_single = 0;  // rows whose only item wrote y directly (k_att_h32)
   if (c.items > 0) {  // no edges: no items, the reduce alone writes the empty rows
     const bool elr = sf == GTA_SF_EXP_LEAKY_RELU;  // GAT's score function, specialised
-    const unsigned xe = bf ? 2u : 4u;              // bytes per gathered element
-    // the generic G-lane attention form <VW, U, ATT, SFC (elr fixed at compile time), G, SH, BF>
-    auto seg4 = [&](auto VW, auto U, auto G, dim3 grid, int lanes_per_head) {
+    // the generic G-lane attention form <VW, U, ATT, SFC (elr fixed at compile time), G, SH, ET>; F8: the
+    // fp8 shapes (G = 16, VW = F/16 at every width)
+    auto seg4 = [&](auto VW, auto U, auto G, dim3 grid, int lanes_per_head, auto F8) {
       with_bools([&](auto ELR, auto SH, auto BF) {
-        k_agg_seg4<VW(), U(), false, 0, true, (ELR() ? GTA_SF_EXP_LEAKY_RELU : -1), G(), SH(), BF()>
+        constexpr int ET = F8() ? E_FP8 : (BF() ? E_BF16 : E_F32);
+        k_agg_seg4<VW(), U(), false, 0, true, (ELR() ? GTA_SF_EXP_LEAKY_RELU : -1), G(), SH(), ET>
             <<<grid, c.blk, 0, c.s>>>(indices, c.nit, x, ldx, nullptr, 0, lanes_per_head, c.slabs, c.its, att);
       }, elr, shifted, bf);
     };
+    constexpr BC<true> fp8{};
+    constexpr BC<false> wide{};
     const int lph32 = static_cast<int>((F / heads) / 4);
-    const bool lean = tuning().att_lean && elr && F == 128 && heads == 8 && lean32_ok(n_cols, ldx, xe) &&
+    const bool lean = !f8 && tuning().att_lean && elr && F == 128 && heads == 8 && lean32_ok(n_cols, ldx, xe) &&
                       lean32_ok(n_cols, ldb, 4u);
-    if (lean) {
+    if (f8) {  // no lean fp8 attention kernel
+      if (vq == 4) seg4(IC<4>{}, IC<8>{}, IC<16>{}, c.g4, lph, fp8);
+      else if (vq == 8) seg4(IC<8>{}, IC<8>{}, IC<16>{}, c.g4, lph, fp8);
+      else seg4(IC<16>{}, IC<8>{}, IC<16>{}, c.g4, lph, fp8);
+    } else if (lean) {
       const uint32_t rb = static_cast<uint32_t>(ldx * xe), bbytes = static_cast<uint32_t>(ldb * 4);
       // single-item rows are common only when few blocks cut the rows (low degree, B <= 2); above
       // that the row_ptr reads at every item's end cost more than the rare direct writes save
@@ -6238,11 +6405,11 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
                                                            c.its, rp, normalize, y, ldy, sums, sf_out, shift);
       }, shifted, bf);
     } else if (F == 128 && (F / heads) % 4 == 0 && lph32 >= 1 && 32 % lph32 == 0) {
-      seg4(IC<4>{}, IC<8>{}, IC<32>{}, c.g2h, lph32);
+      seg4(IC<4>{}, IC<8>{}, IC<32>{}, c.g2h, lph32, wide);
     } else if (vq == 4) {
-      seg4(IC<4>{}, IC<4>{}, IC<16>{}, c.g4, lph);
+      seg4(IC<4>{}, IC<4>{}, IC<16>{}, c.g4, lph, wide);
     } else {
-      seg4(IC<16>{}, IC<2>{}, IC<16>{}, c.g4, lph);
+      seg4(IC<16>{}, IC<2>{}, IC<16>{}, c.g4, lph, wide);
     }
     GTA_LAUNCHED("k_agg_seg4<att>");
   }

@@ -268,8 +268,14 @@ class Executor:
         #   same cast table -- rounding commutes with the max -- and under this option only, MEAN runs
         #   as the blocked aggregate with row_scale = 1 / deg.  Left as they are: the row-chunked form
         #   (tables under the size gate), expression gathers, self-term forms, ORDER C and distributed.py.
-        if gather_dtype not in (None, torch.float32, torch.bfloat16):
-            raise ValueError(f"gather_dtype: None, torch.float32 or torch.bfloat16, not {gather_dtype}")
+        #   torch.float8_e4m3fn (FP8): the same route for the ADD aggregates and the fused attention
+        #   aggregate with ops.to_fp8 as the cast and one byte per element in the size gate and
+        #   auto_blocks -- bitwise the fp32 run on the rounded table.  No scaling: tables are rounded
+        #   as they are, so values below 2^-10 round to 0 and |x| > 448 saturates.  The MAX / MIN,
+        #   MEAN and multi-reducer routes take no fp8 and keep gathering the uncast table.
+        if gather_dtype not in (None, torch.float32, torch.bfloat16, FP8):
+            raise ValueError("gather_dtype: None, torch.float32, torch.bfloat16 or torch.float8_e4m3fn, "
+                             f"not {gather_dtype}")
         self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
         self.gather_casts = 0
         self._gather_cache = {}  # id(table) -> (table, its version, the bf16 copy): identity checked on use
@@ -673,7 +679,8 @@ class Executor:
         F, H = x.shape[1], a.shape[1]
         if x.dtype not in ops.BlockedPlan.DTYPES or not ops.BlockedPlan.supports_att(F, H):
             return None
-        xe = 2 if self.gather_dtype == torch.bfloat16 else x.element_size()  # bytes per gathered element
+        xe = 1 if self.gather_dtype == FP8 and x.dtype == torch.float32 else (
+            2 if self.gather_dtype == torch.bfloat16 else x.element_size())  # bytes per gathered element
         B = self.attention_blocks or ops.BlockedPlan.auto_blocks(self.graph, F, xe)
         # the lean fused kernel (F = 128, 8 heads) beats softmax + aggregate even unblocked (B = 1:
         # Flickr 102 vs 168 us; the round-4 probe, profiles/r04/layer_bench_*.log); other shapes need a blocked table
@@ -940,7 +947,7 @@ class Executor:
         if op.comp in MOMENTS:  # one member: the same kernel family, the moment accumulators only
             B = self._multi_blocks((op.comp,), v, t, g, col)
             if B:
-                tb = t if col else self._gather_cast(t)
+                tb = t if col else self._gather_cast(t, reduce=True)
                 y, = ops.reduce_multi_blocked(g, tb, (op.comp,), blocks=B, std_eps=self.std_eps)
                 self._count(self._gather_bytes(E, n_out, F, tb.element_size()))
                 return NodeT(y)
@@ -958,11 +965,11 @@ class Executor:
         if self.reduce_blocked and scat:
             on = self.gather_dtype == torch.bfloat16
             if not col and v.mode == "src" and (op.comp != "MEAN" or on):
-                B = self._blocked_blocks(t, "src", 0)
+                B = self._blocked_blocks(t, "src", 0, reduce=True)
             elif col and v.mode == "dst" and op.comp != "MEAN":
-                B = self._blocked_blocks(t, "src", 0, g)
+                B = self._blocked_blocks(t, "src", 0, g, reduce=True)
         if B:
-            tb = t if col else self._gather_cast(t)
+            tb = t if col else self._gather_cast(t, reduce=True)
             nbytes = self._gather_bytes(E, n_out, F, tb.element_size())
             if op.comp == "MEAN":
                 y = ops.aggregate_blocked(g, tb, None, row_scale=_mean_scale(g), blocks=B)
@@ -984,9 +991,9 @@ class Executor:
         if not (self.reduce_blocked and isinstance(v, Scat)):
             return False
         if not col and v.mode == "src" and (comp != "MEAN" or self.gather_dtype == torch.bfloat16):
-            return bool(self._blocked_blocks(t, "src", 0))
+            return bool(self._blocked_blocks(t, "src", 0, reduce=True))
         if col and v.mode == "dst" and comp != "MEAN":
-            return bool(self._blocked_blocks(t, "src", 0, g))
+            return bool(self._blocked_blocks(t, "src", 0, g, reduce=True))
         return False
 
     def _multi_blocks(self, reds, v, t, g, col):
@@ -997,7 +1004,8 @@ class Executor:
             return 0
         if v.mode != ("dst" if col else "src"):
             return 0
-        return self._blocked_blocks(t, "src", 0, g if col else None, planes=ops.reduce_multi_planes(reds))
+        return self._blocked_blocks(t, "src", 0, g if col else None, planes=ops.reduce_multi_planes(reds),
+                                    reduce=True)
 
     def _multi_wanted(self, group, v, t, g, col):
         """Without multi_reduce_blocked the group launch runs row-chunked only: where every member would
@@ -1020,7 +1028,7 @@ class Executor:
         the operand read once, one output per member."""
         reds = tuple(self.g.ops[i].comp for i in group)
         if blocks:
-            t = t if self.g.ops[group[0]].order == "C" else self._gather_cast(t)
+            t = t if self.g.ops[group[0]].order == "C" else self._gather_cast(t, reduce=True)
             ys = ops.reduce_multi_blocked(g, t, reds, blocks=blocks, std_eps=self.std_eps)
             index, row_es = True, t.element_size()
         else:
@@ -1094,20 +1102,28 @@ class Executor:
             return ops.aggregate_blocked(g, xt, wt, out=acc, accumulate=acc is not None, blocks=B)
         return ops.aggregate(g, xt, mode, wt, out=acc, accumulate=acc is not None, plan=self._plan())
 
-    def _blocked_blocks(self, xt, mode, heads, graph=None, planes=1):
+    def _cast_dtype(self, reduce=False):
+        """gather_dtype as a route sees it: the reducers (reduce) take no fp8 and see the option off."""
+        return None if reduce and self.gather_dtype == FP8 else self.gather_dtype
+
+    def _blocked_blocks(self, xt, mode, heads, graph=None, planes=1, reduce=False):
         """Column blocks of the blocked aggregate for this gathered table, or 0 for the row-chunked
         form: a source table of at least blocked_min_table_bytes (its own element size) of a dtype
-        and width the blocked kernels take.  planes: partial rows per item (BlockedPlan.auto_blocks)."""
+        and width the blocked kernels take.  planes: partial rows per item (BlockedPlan.auto_blocks).
+        reduce: the gate of a reducer route (_cast_dtype)."""
         g = self.graph if graph is None else graph
         # the table as it will be gathered: with gather_dtype bf16, _spmm rounds an fp32 table of the
         # layer's own CSR (not of the ORDER-C views) to bf16, and a bf16 table is taken as it is; with
         # the option off only fp32 tables take the blocked form
-        on = self.gather_dtype == torch.bfloat16
-        dt = torch.bfloat16 if on and xt.dtype == torch.float32 and graph is None else xt.dtype
-        es = 2 if dt == torch.bfloat16 else xt.element_size()
-        if not (mode == "src" and self.blocked_blocks and (dt == torch.float32 or (on and dt == torch.bfloat16))
-                and xt.shape[0] * xt.shape[1] * es >= self.blocked_min_table_bytes
-                and ops.BlockedPlan.supports(xt.shape[1], heads, dt)):
+        # (gather_dtype fp8: the same with e4m3 and one byte per element, for the aggregates alone)
+        gd = self._cast_dtype(reduce)
+        on = gd is not None
+        dt = gd if on and xt.dtype == torch.float32 and graph is None else xt.dtype
+        es = 1 if dt == FP8 else (2 if dt == torch.bfloat16 else xt.element_size())
+        fits = ops.BlockedPlan.supports_fp8(xt.shape[1], heads) if dt == FP8 else \
+            ops.BlockedPlan.supports(xt.shape[1], heads, dt)
+        if not (mode == "src" and self.blocked_blocks and (dt == torch.float32 or (on and dt == gd))
+                and xt.shape[0] * xt.shape[1] * es >= self.blocked_min_table_bytes and fits):
             return 0
         B = self.blocked_blocks
         if B == "auto":
@@ -1116,15 +1132,19 @@ class Executor:
             B = B if B >= 4 else 0
         return B if B and g.blocked_plan(B).sorted else 0
 
-    def _gather_cast(self, t):
+    def _gather_cast(self, t, reduce=False):
         """The node table t as the blocked kernels gather it under gather_dtype: t itself (no option,
-        or t already of that type), else its RNE rounding to bf16 -- made once per table value and
-        shared by its consumers (_memo: identity and version checked)."""
-        if self.gather_dtype != torch.bfloat16 or t.dtype != torch.float32:
+        or t already of that type), else its RNE rounding to bf16, or to e4m3 by ops.to_fp8 -- made
+        once per table value and shared by its consumers (_memo: identity and version checked).
+        reduce: for a reducer route (_cast_dtype)."""
+        gd = self._cast_dtype(reduce)
+        if gd is None or t.dtype != torch.float32:
             return t
         def cast():
-            self._count(t.shape[0] * t.shape[1] * 6)
+            self._count(t.shape[0] * t.shape[1] * (5 if gd == FP8 else 6))
             self.gather_casts += 1
+            if gd == FP8:
+                return ops.to_fp8(t)
             return ops.pitched(t.to(torch.bfloat16))
         return _memo(self._gather_cache, id(t), t, cast)
 
@@ -1496,6 +1516,7 @@ def aggregate_trace(events):
 # shape, stride), the calling thread's libgta knob state (ops.knob_state) and stays eager on a stream with an attached
 # knob set; weights changed in place are re-transposed into the graph's W^T before the replay.
 FUSE_MLP = True  # default of Executor.fuse_mlp (layer benches A/B it)
+FP8 = torch.float8_e4m3fn  # Executor.gather_dtype: OCP e4m3 gathered tables (ops.to_fp8)
 MLP_BF16_SUM = True  # default of Executor.mlp_bf16_sum: GIN's sum stored in bf16 for the fused MLP (ABI 10)
 AUTO_GRAPH = True
 AUTO_GRAPH_MAX_EDGES = 1 << 40  # every graph (round 3: 1 << 23, launch-bound layers only)

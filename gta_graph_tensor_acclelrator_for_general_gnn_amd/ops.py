@@ -111,6 +111,36 @@ def pitched(t):
     return out
 
 
+FP8 = torch.float8_e4m3fn  # OCP e4m3: what GTA_FP8 tables hold
+FP8_MAX = 448.0
+
+
+def to_fp8(t):
+    """t as an e4m3 (torch.float8_e4m3fn) node table for aggregate_blocked / gat_aggregate_blocked:
+    clamped to +-448 (torch's cast does not saturate: 500 would become NaN), NaN kept, then rounded
+    to nearest even by Tensor.to, on storage whose rows are 16-B aligned (pitch a multiple of 16
+    bytes, padding zero).  No scaling: values are rounded as they are, so |x| > 448 saturates and
+    values below 2^-10 round to 0.  Pure torch, on any device; the CPU cast is the definition."""
+    if t.dim() != 2:
+        raise ValueError("to_fp8: a 2-D table")
+    r = t.float().clamp(-FP8_MAX, FP8_MAX).to(FP8)  # clamp keeps NaN
+    n, F = r.shape
+    P = -(-F // 16) * 16
+    if P == F and r.is_contiguous() and r.data_ptr() % 16 == 0:
+        return r
+    buf = torch.zeros(n, P, dtype=torch.uint8, device=r.device).view(FP8)
+    buf[:, :F].view(torch.uint8).copy_(r.view(torch.uint8))
+    return buf[:, :F]
+
+
+def _fp8_rows(x, who):
+    """ldx (bytes) of an e4m3 table the blocked kernels take: 16-B aligned rows."""
+    ldx = _rows(x, "x", FP8)
+    if ldx % 16 or x.data_ptr() % 16:
+        raise ValueError(f"{who}: an fp8 x needs 16-B aligned rows (ldx % 16 == 0; ops.to_fp8 lays them out)")
+    return ldx
+
+
 def _sf(sf):
     if sf is None:
         return 0
@@ -509,6 +539,17 @@ class BlockedPlan:
         return int(max(1, min(24, round(table_mb / 6.0), avg_deg // (24 * int(planes)))))
 
     @staticmethod
+    def supports_fp8(F, heads):
+        """Shapes the blocked kernels take for an e4m3 table (the aggregate, and with heads >= 1 the
+        fused attention aggregate): F in {64, 128, 256}, quarter-wave items at every width, so with
+        head weights lanes per head (F/heads)/(F/16) in {1, 2, 4, 8, 16}."""
+        if F not in (64, 128, 256):
+            return False
+        if not heads:
+            return True
+        return BlockedPlan.supports_att(F, heads)
+
+    @staticmethod
     def supports(F, heads, dtype=torch.float32):
         """Shapes libgta's blocked kernels take: an fp32 or bf16 table, F in {64, 128, 256} and, with
         head weights, the quarter-wave form's lanes per head (F/heads)/(F/16) in {1, 2, 4, 8, 16} or
@@ -531,13 +572,16 @@ def aggregate_blocked(graph, x, w=None, row_scale=None, out=None, accumulate=Fal
     gathered X slice stays L2-resident.  single_launch: one launch over (block, row) items into per-block
     slabs + an ordered reduce; otherwise B dependent launches accumulating into out.
     x: fp32, or bf16 (gta_aggregate_blocked_x: rows widened exactly, every sum in fp32 -- bitwise the
-    call on x.float(); needs 16-B aligned rows, ldx % 8 == 0, as node_table / pitched make them)."""
+    call on x.float(); needs 16-B aligned rows, ldx % 8 == 0, as node_table / pitched make them),
+    or e4m3 (torch.float8_e4m3fn, as to_fp8 makes it: the same contract, every code widened exactly;
+    16-B aligned rows, ldx % 16 == 0; quarter-wave items, BlockedPlan.supports_fp8)."""
     _need_gpu(x, w, row_scale, out, graph.indptr)
     F = x.shape[1]
-    if x.dtype not in BlockedPlan.DTYPES:
+    f8 = x.dtype == FP8
+    if x.dtype not in BlockedPlan.DTYPES and not f8:
         raise ValueError(f"aggregate_blocked: unsupported dtype={x.dtype}")
     bf = x.dtype == torch.bfloat16
-    ldx = _rows(x, "x", x.dtype)
+    ldx = _fp8_rows(x, "aggregate_blocked") if f8 else _rows(x, "x", x.dtype)
     if bf and (ldx % 8 or x.data_ptr() % 16):
         raise ValueError("aggregate_blocked: a bf16 x needs 16-B aligned rows (ldx % 8 == 0)")
     if x.shape[0] < graph.n_cols:
@@ -548,7 +592,7 @@ def aggregate_blocked(graph, x, w=None, row_scale=None, out=None, accumulate=Fal
             w = w.view(-1, 1)
         ldw = _rows(w, "w")
         heads = w.shape[1]
-    if not BlockedPlan.supports(F, heads, x.dtype):
+    if not (BlockedPlan.supports_fp8(F, heads) if f8 else BlockedPlan.supports(F, heads, x.dtype)):
         raise ValueError(f"aggregate_blocked: unsupported F={F}, heads={heads}, dtype={x.dtype}")
     if plan is None:
         plan = graph.blocked_plan(blocks)
@@ -558,9 +602,9 @@ def aggregate_blocked(graph, x, w=None, row_scale=None, out=None, accumulate=Fal
         out = (torch.zeros if accumulate else torch.empty)(graph.n_rows, F, dtype=torch.float32, device=x.device)
     ldy = _rows(out, "out")
     ws = plan.workspace(F) if single_launch else None
-    if bf:
+    if bf or f8:
         check(_L().gta_aggregate_blocked_x(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols,
-                                           graph.nnz, _ptr(x), ldx, F, _lib.GTA_BF16, _ptr(w), ldw, heads,
+                                           graph.nnz, _ptr(x), ldx, F, _lib.GTA_FP8 if f8 else _lib.GTA_BF16, _ptr(w), ldw, heads,
                                            _ptr(row_scale), _ptr(out), ldy, int(bool(accumulate)), _ptr(plan.buf),
                                            plan.blocks, plan.item_edges, _ptr(ws), _stream(x.device)),
               "aggregate_blocked_x")
@@ -686,7 +730,8 @@ def gat_aggregate_blocked(graph, x, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize
     shift: None, or the row-max table of softmax_shift for the same graph, scores and sf: the
     overflow-safe form (gta_gat_aggregate_blocked_shifted), v = exp(g(a + b) - shift[dst]).
     x: fp32, or bf16 (gta_gat_aggregate_blocked_x, shifted or not: bitwise the call on x.float();
-    16-B aligned rows, ldx % 8 == 0); the score tables, out and sums stay fp32."""
+    16-B aligned rows, ldx % 8 == 0), or e4m3 (to_fp8: the same contract; ldx % 16 == 0); the score
+    tables, out and sums stay fp32."""
     _need_gpu(x, a_dst, b_src, out, sums, shift, graph.indptr)
     F, H = x.shape[1], a_dst.shape[1]
     if b_src.shape[1] != H:
@@ -706,16 +751,17 @@ def gat_aggregate_blocked(graph, x, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize
     if sums is not None and (not sums.is_contiguous() or tuple(sums.shape) != (graph.n_rows, H)):
         raise ValueError("gat_aggregate_blocked: sums must be a contiguous [N, heads] tensor")
     ws = plan.workspace_att(F, H)
-    if x.dtype == torch.bfloat16:
-        ldx = _rows(x, "x", torch.bfloat16)
-        if ldx % 8 or x.data_ptr() % 16:
+    if x.dtype in (torch.bfloat16, FP8):
+        f8 = x.dtype == FP8
+        ldx = _fp8_rows(x, "gat_aggregate_blocked") if f8 else _rows(x, "x", torch.bfloat16)
+        if not f8 and (ldx % 8 or x.data_ptr() % 16):
             raise ValueError("gat_aggregate_blocked: a bf16 x needs 16-B aligned rows (ldx % 8 == 0)")
         if shift is not None:
             _shift_table(graph, shift, H, "gat_aggregate_blocked")
         check(_L().gta_gat_aggregate_blocked_x(
             _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols, graph.nnz, _ptr(x), ldx, F,
-            _lib.GTA_BF16, _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"), H, _sf(sf),
-            1 if normalize else 0, _sf(sf_out), _ptr(out), _rows(out, "out"), _ptr(sums), _ptr(plan.buf), plan.blocks,
+            _lib.GTA_FP8 if f8 else _lib.GTA_BF16, _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"),
+            H, _sf(sf), 1 if normalize else 0, _sf(sf_out), _ptr(out), _rows(out, "out"), _ptr(sums), _ptr(plan.buf), plan.blocks,
             plan.item_edges, _ptr(ws), _ptr(shift), _stream(x.device)), "gat_aggregate_blocked_x")
         return out, sums
     if shift is not None:

@@ -31,12 +31,15 @@ class Layer:
         stable_softmax: run() evaluates the layer's softmax chains overflow-safe, exp(s - row max)
         (Executor.softmax_shift); off, the default, is the unshifted path.
         gather_dtype: None (the default: nothing changes) or torch.bfloat16 -- run() stores the node
-        tables its column-blocked aggregates gather as bf16 (Executor.gather_dtype).
+        tables its column-blocked aggregates gather as bf16 (Executor.gather_dtype) -- or
+        torch.float8_e4m3fn: as OCP e4m3 (ops.to_fp8; no scaling, so values below 2^-10 round to 0
+        and |x| > 448 saturates; the reducers keep the uncast table).
         multi_reduce_blocked: False (the default: nothing changes) or True -- run() sends sibling
         gathers and lone VAR / STD gathers of a source table beyond L2 through one column-blocked
         gta_reduce_multi_blocked launch (Executor.multi_reduce_blocked)."""
-        if gather_dtype not in (None, torch.float32, torch.bfloat16):
-            raise ValueError(f"gather_dtype: None, torch.float32 or torch.bfloat16, not {gather_dtype}")
+        if gather_dtype not in (None, torch.float32, torch.bfloat16, torch.float8_e4m3fn):
+            raise ValueError("gather_dtype: None, torch.float32, torch.bfloat16 or torch.float8_e4m3fn, "
+                             f"not {gather_dtype}")
         self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
         self.network, self.layer, self.reorder = network, layer, reorder
         multi = isinstance(aggregator, (tuple, list))

@@ -56,14 +56,20 @@ extern "C" {
                               gta_gat_aggregate_blocked_x; no existing signature changes);
                               15 (additive): gta_reduce_blocked (column-blocked gather MAX / MIN);
                               15 (additive): gta_reduce_multi (MEAN / MAX / MIN / VAR / STD in one pass);
-                              15 (additive): gta_reduce_multi_blocked (the same, column-blocked) */
+                              15 (additive): gta_reduce_multi_blocked (the same, column-blocked);
+                              15 (additive): GTA_FP8 gathered tables in gta_aggregate_blocked_x and
+                              gta_gat_aggregate_blocked_x (no new symbol, no signature changes) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
 
 /* dtypes; GTA_F32_BF16 (update_mm only): fp32 x rounded to bf16 (RNE) as it is
- * staged into LDS, bf16 W -- no separate cast pass over x */
-enum { GTA_F32 = 0, GTA_BF16 = 1, GTA_F32_BF16 = 2 };
+ * staged into LDS, bf16 W -- no separate cast pass over x.
+ * GTA_FP8 (gta_aggregate_blocked_x / gta_gat_aggregate_blocked_x only): OCP e4m3fn, one byte per
+ * element -- sign s, exponent e (4 bits), mantissa m (3 bits): +-m 2^-9 for e = 0 (denormals),
+ * +-(1 + m/8) 2^(e-7) otherwise, largest value 448; no infinities, codes 0x7f / 0xff are NaN,
+ * 0x80 is -0. */
+enum { GTA_F32 = 0, GTA_BF16 = 1, GTA_F32_BF16 = 2, GTA_FP8 = 3 };
 
 /* Scatter direction (reference ISA `scatter` DIRECTION dst/src,
  * template/ISA_defination.yaml:33-44; op ORDER R/C in the op YAML). */
@@ -370,7 +376,21 @@ int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int
  * needs n_cols < 2^24 and n_cols * ldx * 2 < 2^32 (larger tables take the 64-bit form).
  * shift (gta_gat_aggregate_blocked_x): NULL = unshifted; else the table of gta_softmax_shift and
  * the shifted form's restriction on sf (GTA_SF_EXP_LEAKY_RELU or GTA_SF_EXP, else
- * GTA_ERR_UNSUPPORTED), for either x_dtype. */
+ * GTA_ERR_UNSUPPORTED), for every x_dtype.
+ * GTA_FP8 (ABI 15 additive; these two entry points alone, every other one keeps refusing it): x holds
+ * e4m3 rows, one byte per element, ldx in BYTES.  The contract is bf16's: every gathered element
+ * widens to fp32 exactly (all 256 codes: denormals, -0 and the two NaN codes included) and enters
+ * the fp32 kernel's per-column chain in the item's edge order, with the same per-head sums of v,
+ * so a GTA_FP8 call is BITWISE EQUAL to the GTA_F32 call on the widened table with the same plan,
+ * blocks, item_edges and knobs -- whatever the lane layout: each column keeps one accumulator per
+ * item and the plan fixes the items.  The kernels run quarter-wave items at every width (16 lanes
+ * x F/16 bytes: four 128-B rows per wave instruction at F = 128; knob seg_lean = 2 selects a lean
+ * form there for the plain aggregate -- unweighted, one weight per edge or 8 head weights -- which
+ * is bitwise equal to the generic one that seg_lean = 0 / 1 run and, as measured, slower).  Alignment: x 16-B aligned, ldx % 16 == 0; a misaligned table, or head weights
+ * that do not fit (F / heads not a multiple of F / 16, lanes per head not dividing 16), return
+ * GTA_ERR_UNSUPPORTED.  The lean form's 32-bit addressing needs n_cols < 2^24 and n_cols * ldx <
+ * 2^32 (larger tables take the 64-bit form).  w, row_scale, the score tables, shift, y, sums, the
+ * slabs, plans, workspaces and size functions are unchanged. */
 int gta_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols, int64_t nnz,
                             const void* x, int64_t ldx, int64_t F, int x_dtype, const float* w, int64_t ldw,
                             int64_t heads, const float* row_scale, float* y, int64_t ldy, int accumulate,

@@ -54,7 +54,8 @@ def demangle(symbols):
 
 def pair_defaulted(old, new):
     """A kernel template that gained a trailing parameter defaulted to false (and perhaps an argument
-    that instantiation never reads) changes its symbol: NEW's k<..., false> is OLD's k<...>.  Renames
+    that instantiation never reads), or whose trailing bool became an int, changes its symbol: NEW's
+    k<..., false> is OLD's k<...>, NEW's k<..., 0> OLD's k<..., false>.  Renames
     such NEW entries to OLD's symbol so the two are compared; returns how many were paired."""
     by_name = {d: f for f, d in demangle(old.keys() - new.keys()).items()}
     n = 0
@@ -62,6 +63,12 @@ def pair_defaulted(old, new):
         if d.endswith(", false") and d[:-len(", false")] in by_name:
             new[by_name[d[:-len(", false")]]] = new.pop(f)
             n += 1
+            continue
+        # a trailing bool that became an int (k_agg_seg4's BF -> its element type): 0 / 1 are false / true
+        for num, flag in ((", 0>", ", false>"), (", 1>", ", true>")):
+            if (d + ">").endswith(num) and (d + ">")[:-len(num)] + flag in {o + ">" for o in by_name}:
+                new[by_name[((d + ">")[:-len(num)] + flag)[:-1]]] = new.pop(f)
+                n += 1
     return n
 
 
@@ -69,7 +76,8 @@ def main(argv):
     old, new = kernels(argv[1], argv[3:]), kernels(argv[2], argv[3:])
     paired = pair_defaulted(old, new)
     if paired:
-        print(f"{paired} kernels of NEW paired with OLD's symbol (a trailing template parameter defaulted to false)")
+        print(f"{paired} kernels of NEW paired with OLD's symbol (a trailing template parameter defaulted to false, "
+              "or a trailing bool that became an int)")
     for f in sorted(old.keys() ^ new.keys()):
         print("only in OLD" if f in old else "only in NEW", f)
     differ = 0

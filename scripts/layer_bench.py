@@ -95,9 +95,9 @@ if __name__ == "__main__":
     if "--no-mlp" in sys.argv[1:]:  # the GIN MLP as two UPDATE launches (A/B of the fused chain)
         executor.FUSE_MLP = False
     gdt = None
-    if "--gather-dtype" in argv:  # f32 (as they are) or bf16: Executor.gather_dtype for every layer
+    if "--gather-dtype" in argv:  # f32 (as they are), bf16 or fp8: Executor.gather_dtype for every layer
         i = argv.index("--gather-dtype")
-        gdt = {"f32": None, "bf16": torch.bfloat16}[argv[i + 1]]
+        gdt = {"f32": None, "bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}[argv[i + 1]]
         del argv[i:i + 2]
     if "--mm-rows-min" in argv:  # ops.MM_ROWS_MIN_M: smallest M for the row-streaming UPDATE entry
         i = argv.index("--mm-rows-min")
