@@ -1315,6 +1315,11 @@ __device__ __forceinline__ float load_elem(const uint8_t* p) {  // one e4m3 code
   return __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(*p), false)[0];
 }
 
+// generic -> LDS address space, and the 32-bit LDS byte address (macros: a __device__ helper
+// taking or returning address-space-3 pointers keeps hipcc from emitting a template kernel's host stub)
+#define GTA_TO_LDS(p) ((__attribute__((address_space(3))) void*)(p))
+#define GTA_LDS_ADDR(p) static_cast<uint32_t>(reinterpret_cast<uintptr_t>(GTA_TO_LDS(p)))
+
 // ---- what the blocked item kernels share: item decode, row loads, slab-row store, the fold ----
 
 // The wave's items: G lanes each (16: four per wave, 32: two), lane group j takes item
@@ -1699,7 +1704,49 @@ __device__ __forceinline__ void a1_spread(const float2 pr, const bool odd, float
 // lane order -- one select per 32 edges, then the walk's fixed broadcasts.  Items are clamped to
 // nnz: no index or weight outside [0, nnz) is read.  Same per-lane edge order and fma chain as
 // the A1 form: bitwise equal to it.
-template <int NT, bool BF>
+//
+// AL (knob seg_alpha_lds): the grid walk with its weights staged in LDS a chunk ahead by
+// global_load_lds_dwordx4 (no destination VGPRs).  The wave owns 4 KiB: two buffers of 2 KiB, a
+// buffer = the two staging instructions' 1-KiB images, instruction k = edges 16 k .. 16 k + 15 of
+// the chunk: lane l of item j writes bytes [16 l, 16 l + 16) of those 512 B at j * 512 (the
+// hardware's lane slots: M0 base + 16 * lane id).  A lane whose 16 B -- four heads of one edge --
+// lie outside the item is masked out of the load, so no weight outside [beg, end) is read and a
+// neighbour's never reaches LDS.  At the top of chunk c the wave stages chunk c + 1 into the other
+// buffer (chunk 0 in the prologue, ahead of the index loads) and waits with a counted vmcnt that
+// leaves only those two staging loads outstanding; lane (h, q) then reads edge e's weight of its
+// head at (e >> 4) * 1024 + j * 512 + (e & 15) * 32 + 4 h -- eight lanes per address, a broadcast
+// -- instead of the 8-B load and its DPP spread.  A masked edge's weight is +0 by the gathers' own
+// per-edge test, so a stale LDS word is never used.  The region is wave-private: no barrier.  Same
+// weights, edge order and fma chain: bitwise equal to the grid walk.
+__device__ __forceinline__ char* alpha_stage_lds() {  // 4 KiB per wave
+  __shared__ __attribute__((aligned(16))) char a[kWavesPerBlock * 4096];
+  return a;
+}
+// the lane's eight weights of step S (edges S .. S + 7 of the chunk) from the buffer at LDS byte
+// address la; one asm statement with its wait, so no register is touched while a read is in flight
+template <int S>
+__device__ __forceinline__ void alpha_lds_read(float (&wu)[8], uint32_t la) {
+  constexpr int B = (S >> 4) * 1024 + (S & 15) * 32;
+  asm volatile(
+      "ds_read_b32 %0, %8 offset:%9\n\tds_read_b32 %1, %8 offset:%10\n\t"
+      "ds_read_b32 %2, %8 offset:%11\n\tds_read_b32 %3, %8 offset:%12\n\t"
+      "ds_read_b32 %4, %8 offset:%13\n\tds_read_b32 %5, %8 offset:%14\n\t"
+      "ds_read_b32 %6, %8 offset:%15\n\tds_read_b32 %7, %8 offset:%16\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(wu[0]), "=&v"(wu[1]), "=&v"(wu[2]), "=&v"(wu[3]), "=&v"(wu[4]), "=&v"(wu[5]), "=&v"(wu[6]), "=&v"(wu[7])
+      : "v"(la), "i"(B), "i"(B + 32), "i"(B + 64), "i"(B + 96), "i"(B + 128), "i"(B + 160), "i"(B + 192), "i"(B + 224)
+      : "memory");
+}
+__device__ __forceinline__ void alpha_lds_read(float (&wu)[8], uint32_t la, int s) {  // s: 0, 8, 16, 24 (unrolled)
+  switch (s) {
+    case 0: alpha_lds_read<0>(wu, la); break;
+    case 8: alpha_lds_read<8>(wu, la); break;
+    case 16: alpha_lds_read<16>(wu, la); break;
+    default: alpha_lds_read<24>(wu, la); break;
+  }
+}
+
+template <int NT, bool BF, bool AL = false>
 __device__ __forceinline__ void h32_grid_walk(const int32_t* indices, const int64_t* n_items_p,
                                               const float* x, uint32_t row_bytes, const float* w,
                                               uint32_t nnz, float* slabs, const SegItem* items) {
@@ -1737,12 +1784,44 @@ __device__ __forceinline__ void h32_grid_walk(const int32_t* indices, const int6
   };
   auto wld = [&](uint32_t off) { return *reinterpret_cast<const float2*>(wbase + off); };
   auto row = [&](int src) { return lean_at<XR>(xb, src, row_bytes, colb); };
+  // AL: the wave's LDS region, the lane's read address in the current buffer, its staging source
+  char* wlds = nullptr;
+  uint32_t la = 0u, doff = 0u;
+  int sbuf = 0;  // the buffer the next staging fills (wave-uniform)
+  auto stage = [&](int c) __attribute__((always_inline)) {  // the chunk at grid edge c into buffer sbuf
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int e = c + 16 * k + (l32 >> 1) - f;  // the lane's edge, counted from beg
+      if (static_cast<uint32_t>(e) < len)
+        __builtin_amdgcn_global_load_lds(const_cast<char*>(wbase + (doff + static_cast<uint32_t>(k) * 512u)),
+                                         GTA_TO_LDS(wlds + sbuf * 2048 + k * 1024), 16, 0, 0);
+    }
+    sbuf ^= 1;
+    doff += static_cast<uint32_t>(G) * 32u;
+  };
+  if constexpr (AL) {
+    wlds = alpha_stage_lds() + wave_id_uniform() * 4096;
+    la = GTA_LDS_ADDR(wlds) + static_cast<uint32_t>((lane >> 5) * 512 + h * 4);
+    doff = ((beg & ~7u) + static_cast<uint32_t>(l32 >> 1)) * 32u + static_cast<uint32_t>(l32 & 1) * 16u;
+    stage(0);
+  }
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   const int i0 = ldc(ie);
   int in = ldc(ie + G);
   int idxv = lo ? i0 : in;  // the 32 edges from beg & ~7, lane = edge
   ie += 2 * G;
   for (int c = 0; c < gmax; c += G) {
+    if constexpr (AL) {
+      // chunk c's weights landed: vector loads retire in order, and only the two staging loads of
+      // chunk c + 1 (where there is one) may stay outstanding -- every load after chunk c's staging
+      // is older than they are.  The reads of the buffer being refilled were waited for in chunk c - 1.
+      if (c + G < gmax) {
+        stage(c + G);
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+    }
     const int inn = ldc(ie);  // two chunks ahead: the next 32 edges end in it
 #pragma unroll
     for (int s = 0; s < G; s += U) {
@@ -1752,7 +1831,8 @@ __device__ __forceinline__ void h32_grid_walk(const int32_t* indices, const int6
       if (c + s + U <= gmin && (s > 0 || c > 0 || !front)) {  // inside both items: no masks
 #pragma unroll
         for (int u = 0; u < U; ++u) xv[u] = row(bcastG<G>(idxv, s + u));
-        a1_spread(wld(woff + static_cast<uint32_t>(s) * 32u), odd, wu);
+        if constexpr (AL) alpha_lds_read(wu, la, s);
+        else a1_spread(wld(woff + static_cast<uint32_t>(s) * 32u), odd, wu);
       } else {
         const int p = c + s - f;  // the window's first edge, counted from beg (may be < 0)
         // the masked rows' zeros are written here, before any load of the step is issued: written
@@ -1763,7 +1843,8 @@ __device__ __forceinline__ void h32_grid_walk(const int32_t* indices, const int6
           row4_pin(xv[u]);
         }
         float2 pr = make_float2(0.f, 0.f);
-        if (static_cast<uint32_t>(p + wl) < len) pr = wld(woff + static_cast<uint32_t>(s) * 32u);
+        if constexpr (!AL)
+          if (static_cast<uint32_t>(p + wl) < len) pr = wld(woff + static_cast<uint32_t>(s) * 32u);
         int src[U];  // the eight broadcasts back to back, ahead of the masked gathers
 #pragma unroll
         for (int u = 0; u < U; ++u) src[u] = bcastG<G>(idxv, s + u);
@@ -1771,7 +1852,14 @@ __device__ __forceinline__ void h32_grid_walk(const int32_t* indices, const int6
         for (int u = 0; u < U; ++u) {
           if (static_cast<uint32_t>(p + u) < len) xv[u] = row(src[u]);
         }
-        a1_spread(pr, odd, wu);  // after the gathers are issued; an edge outside the item: no lane loaded it, w = +0
+        if constexpr (AL) {  // an edge outside the item: its LDS word is stale, w = +0
+          alpha_lds_read(wu, la, s);
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+            if (!(static_cast<uint32_t>(p + u) < len)) wu[u] = 0.f;
+        } else {
+          a1_spread(pr, odd, wu);  // after the gathers are issued; an edge outside the item: no lane loaded it, w = +0
+        }
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -1786,11 +1874,12 @@ __device__ __forceinline__ void h32_grid_walk(const int32_t* indices, const int6
     in = inn;
     ie += G;
     woff += static_cast<uint32_t>(G) * 32u;
+    la ^= 2048u;
   }
   if (len) slab_store<(NT & 2) != 0>(slabs + d.k * F + l32 * 4, acc);
 }
 
-template <bool WEIGHTED, int NT, bool W1 = false, bool A1 = false, bool BF = false, bool GR = false>
+template <bool WEIGHTED, int NT, bool W1 = false, bool A1 = false, bool BF = false, bool GR = false, bool AL = false>
 __global__ void __launch_bounds__(kBlock)
 k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
           uint32_t row_bytes, const float* __restrict__ w, int64_t ldw, float* __restrict__ slabs,
@@ -1801,7 +1890,7 @@ k_agg_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   }
   if constexpr (GR) {  // the A1 walk on the edge grid
     static_assert(WEIGHTED && A1 && !W1, "the grid walk is a form of A1");
-    h32_grid_walk<NT, BF>(indices, n_items_p, x, row_bytes, w, nnz, slabs, items);
+    h32_grid_walk<NT, BF, AL>(indices, n_items_p, x, row_bytes, w, nnz, slabs, items);
     return;
   }
   constexpr int G = 32, F = 128, U = 8;
@@ -4118,10 +4207,6 @@ k_mm_rows(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row
 //   Deeper rings at fewer blocks per CU measured slower on every shape
 //   (profiles/r03/mm_depth_sweep.log, mm_cora_epilogue.log) and are not built.
 // Split K (kslice > 0): block row y contracts k in [y * kslice, +kslice) into output slice y.
-// generic -> LDS address space, and the 32-bit LDS byte address (macros: a __device__ helper
-// taking or returning address-space-3 pointers keeps hipcc from emitting a template kernel's host stub)
-#define GTA_TO_LDS(p) ((__attribute__((address_space(3))) void*)(p))
-#define GTA_LDS_ADDR(p) static_cast<uint32_t>(reinterpret_cast<uintptr_t>(GTA_TO_LDS(p)))
 template <int OFF>
 __device__ __forceinline__ void ds_read16(f32x4& v, uint32_t a) {  // result valid after an lgkmcnt wait
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "i"(OFF));
@@ -5230,6 +5315,8 @@ struct Tuning {
   int seg_alpha1 = 1;      // k_agg_h32 with 8 heads: one 8-B weight load per lane and step (A1) instead of two 4-B
   int seg_grid = 1;        // the A1 form with its steps on the aligned 8-edge grid (ldw == 8, w and indices 128-B
                            // aligned): every weight load two whole lines, every index load one
+  int seg_alpha_lds = 1;   // the grid walk with its weights staged in LDS a 32-edge chunk ahead (global_load_lds,
+                           // no VGPRs: one HBM latency per 32 edges instead of one per 8; 0: the 8-B loads and DPP spread)
   int agg_bf16_vw8 = 4;    // k_aggregate over bf16 rows in 16-B pieces (VW = 8) instead of 8-B pieces:
                            // 0 off, 4 / 8 = row loads in flight per lane and step (1 = 4)
   int agg_w1 = 1;          // k_aggregate with one weight per edge: 64 per load, broadcast (WM_EDGE1); 0 = WM_HEAD
@@ -5303,6 +5390,7 @@ const Knob* find_knob(const char* key) {
       {"seg_lean_w1", &Tuning::seg_lean_w1, nullptr},
       {"seg_alpha1", &Tuning::seg_alpha1, nullptr},
       {"seg_grid", &Tuning::seg_grid, nullptr},
+      {"seg_alpha_lds", &Tuning::seg_alpha_lds, nullptr},
       {"seg_pf", &Tuning::seg_pf, nullptr},
       {"agg_bf16_vw8", &Tuning::agg_bf16_vw8, nullptr},
       {"agg_w1", &Tuning::agg_w1, nullptr},
@@ -6121,10 +6209,10 @@ static int aggregate_blocked_impl(const std::string& who, const int64_t* indptr,
         else k_agg_h32pf<3, 64, 0, 8><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, w, ldw, c.slabs, c.its, wbytes, ibytes);
 #undef GTA_PF
       } else if (grid) {
-        with_bools([&](auto BF) {
-          k_agg_h32<true, 3, false, true, BF(), true><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, w, ldw, c.slabs,
-                                                                                c.its, static_cast<uint32_t>(nnz));
-        }, bf);
+        with_bools([&](auto BF, auto AL) {  // AL: the weights staged in LDS a chunk ahead
+          k_agg_h32<true, 3, false, true, BF(), true, AL()><<<c.g2h, c.blk, 0, c.s>>>(
+              indices, c.nit, x, rb, w, ldw, c.slabs, c.its, static_cast<uint32_t>(nnz));
+        }, bf, tuning().seg_alpha_lds != 0);
       } else if (a1) h32(yes, IC<3>{}, no, yes);
       else if (w) h32(yes, IC<3>{}, no, no);
       else h32(no, IC<2>{}, no, no);
