@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libgta.so")
 ABI_VERSION = 15
 
 # enum mirrors of include/gta.h
-GTA_F32, GTA_BF16, GTA_F32_BF16, GTA_FP8 = 0, 1, 2, 3
+GTA_F32, GTA_BF16, GTA_F32_BF16, GTA_FP8, GTA_F32_BF16X3 = 0, 1, 2, 3, 4
 DIR_R, DIR_C = 0, 1
 IDX_EDGE, IDX_SRC, IDX_DST = 0, 1, 2
 OK, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED = 0, -1, -2, -3

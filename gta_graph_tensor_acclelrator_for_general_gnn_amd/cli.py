@@ -76,6 +76,9 @@ def parser():
     p.add_argument("--multi-reduce-blocked", action="store_true",
                    help="sibling gathers and lone VAR / STD gathers of a node table beyond L2 take one column-blocked "
                         "multi-reducer launch (off: the row-chunked launch; the moments' last bits differ)")
+    p.add_argument("--mm-precision", choices=["f32", "bf16x3"], default="f32",
+                   help="fp32 x fp32 MMs: f32 = the fp32 MFMA kernels; bf16x3 = the bf16 MFMA on three-way bf16 splits of "
+                        "both operands (fp32-level accuracy, other last bits)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--reps", type=int, default=3, help="runs per layer; the fastest is reported")
     p.add_argument("--model-edges", type=int, default=1 << 20,
@@ -107,6 +110,8 @@ def run(args, device, log=print):
             kw["gather_dtype"] = GATHER_DTYPES[args.gather_dtype]
         if getattr(args, "multi_reduce_blocked", False):
             kw["multi_reduce_blocked"] = True
+        if getattr(args, "mm_precision", "f32") != "f32":
+            kw["mm_precision"] = args.mm_precision
         lay = None
         for k, (op_array, tile_size_list) in enumerate(c[:2] for c in cands):
             try:

@@ -4857,6 +4857,190 @@ k_mm_ring_bf(const TA* __restrict__ x, int64_t ldx, const int32_t* __restrict__ 
   ring_run<PER_STAGE>(rs, acc, issue, stage, tail, epilogue);
 }
 
+// ---- fp32-accurate UPDATE on the bf16 MFMA (GTA_F32_BF16X3, gta.h "Three-way bf16 split") ----
+// Every fp32 value v is written as v0 + v1 + v2, three bf16 pieces holding its 24 significand bits:
+// v0 = RNE(v), v1 = RNE(v - v0), v2 = RNE((v - v0) - v1), the subtractions exact in fp32.  gfx950's
+// packed v_cvt_pk_bf16_f32 rounds two values at once (NaN stays NaN), widening back is a shift or a
+// mask of the packed pair.  A piece v0 = +-inf (v infinite, or past bf16's largest finite value)
+// gets zero residuals instead of inf - inf = NaN.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, bf16x2_t));
+}
+
+// 8 fp32 values of one lane's fragment -> its three bf16x8 MFMA operands
+__device__ __forceinline__ void bf3_split(const float (&v)[8], bf16x8& p0, bf16x8& p1, bf16x8& p2) {
+  uint32_t h0[4], h1[4], h2[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float a = v[2 * q], b = v[2 * q + 1];
+    h0[q] = cvt_pk_bf16(a, b);
+    const float a0 = __uint_as_float(h0[q] << 16), b0 = __uint_as_float(h0[q] & 0xFFFF0000u);
+    const float ra = __builtin_fabsf(a0) == __builtin_inff() ? 0.f : a - a0;
+    const float rb = __builtin_fabsf(b0) == __builtin_inff() ? 0.f : b - b0;
+    h1[q] = cvt_pk_bf16(ra, rb);
+    const float a1 = __uint_as_float(h1[q] << 16), b1 = __uint_as_float(h1[q] & 0xFFFF0000u);
+    h2[q] = cvt_pk_bf16(ra - a1, rb - b1);
+  }
+  p0 = __builtin_bit_cast(bf16x8, h0);
+  p1 = __builtin_bit_cast(bf16x8, h1);
+  p2 = __builtin_bit_cast(bf16x8, h2);
+}
+
+// A workgroup of 4 waves owns 64 FR rows x BN = 16 NT columns; wave w rows 16 FR w .. +16 FR - 1.
+// K is walked in 32-k steps, ascending.  Per step:
+//   B: the block loads the step's fp32 W^T chunk [BN][32] (thread t: fragment entry (c, lane L = 16 g
+//      + r) with g = t & 3, r = (t >> 2) & 15, c = t >> 6 (+ 4 per further entry): four consecutive
+//      threads read one row's 128 contiguous bytes), splits it in registers and writes the three
+//      planes to LDS in stage_wt_frags' fragment layout (fragment c of plane p at p NT + c KiB, lane
+//      L's 16 B at 16 L; zeros past K and N).  Two buffers: the chunk of step s + 1 is loaded before
+//      step s' MFMAs and split and written after them, into the buffer step s - 1 read; one
+//      __syncthreads() per step orders both.  All four waves read the same planes.
+//   A: lane (g, r) loads x[row r][k0 + 8 g .. +7] of its FR fragments straight to registers (16-, 8-
+//      or 4-B loads by the rows' alignment), the next step's loads issued before this step's MFMAs,
+//      and splits them into three bf16x8 operands per fragment.
+//   Per (A fragment, column fragment) six v_mfma_f32_16x16x32_bf16 into the one accumulator,
+//   smallest terms first: x2 w0, x1 w1, x0 w2, x1 w0, x0 w1, x0 w0.
+// The K tail (K % 32) is one more step with masked loads, zeros past K.  Rows past M read row M - 1
+// and are masked on store.  Plain loads only: every wait is the compiler's.  No atomics, no split K:
+// a row's result depends on that row, W and the shape alone, so FR = 1 and FR = 2 give the same bits.
+template <int NT, int FR>
+__global__ void __launch_bounds__(kBlock, 2)
+k_mm_bf3(const float* __restrict__ x, int64_t ldx, const int32_t* __restrict__ row_idx, int64_t M, int K,
+         const float* __restrict__ wt, int64_t ldwt, int N, int sf, float* __restrict__ out, int64_t ldo) {
+  static_assert(NT == 1 || NT == 2 || NT == 4 || NT == 8, "column fragments");
+  static_assert(FR == 1 || FR == 2, "one or two A fragments per wave");
+  constexpr int BN = 16 * NT, GR = 64 * FR;
+  constexpr int PLANE = NT * 1024, BUF = 3 * PLANE;       // one 32-k step of one plane; its three planes
+  constexpr int WE = (NT * kWave + kBlock - 1) / kBlock;  // W^T fragment entries per thread per step
+  __shared__ __attribute__((aligned(16))) char lds[2 * BUF];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int wv = wave_id_uniform();
+  const int g = lane >> 4, r16 = lane & 15;
+  const int ncb = (N + BN - 1) / BN;
+  const int n0 = static_cast<int>(blockIdx.x % ncb) * BN;
+  const int64_t mw = static_cast<int64_t>(blockIdx.x / ncb) * GR + wv * (16 * FR);
+  const int S = (K + 31) / 32, SFULL = K / 32;  // steps in all, steps wholly inside K
+
+  const float* xr[FR];  // this lane's piece of step 0 in each of its fragment rows
+#pragma unroll
+  for (int i = 0; i < FR; ++i) {
+    const int64_t m = min<int64_t>(mw + 16 * i + r16, M - 1);
+    xr[i] = x + (row_idx ? static_cast<int64_t>(row_idx[m]) : m) * ldx + 8 * g;
+  }
+  const int xal = (ldx % 4 == 0 && aligned(x, 16)) ? 4 : (ldx % 2 == 0 && aligned(x, 8)) ? 2 : 1;
+  auto load_x = [&](float (&v)[FR][8], int s) __attribute__((always_inline)) {
+    const int k = 32 * s;
+#pragma unroll
+    for (int i = 0; i < FR; ++i) {
+      const float* p = xr[i] + k;
+      if (s >= SFULL) {  // the K tail: nothing past K is read
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[i][q] = (k + 8 * g + q < K) ? p[q] : 0.f;
+      } else if (xal == 4) {
+        const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+        v[i][0] = lo.x, v[i][1] = lo.y, v[i][2] = lo.z, v[i][3] = lo.w;
+        v[i][4] = hi.x, v[i][5] = hi.y, v[i][6] = hi.z, v[i][7] = hi.w;
+      } else if (xal == 2) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x2 t2 = *reinterpret_cast<const f32x2*>(p + 2 * q);
+          v[i][2 * q] = t2[0], v[i][2 * q + 1] = t2[1];
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[i][q] = p[q];
+      }
+    }
+  };
+
+  // W^T entries of this thread: source piece of step 0 (row clamped; a row past N stages zeros) and
+  // byte offset inside a plane
+  const float* wr[WE];
+  bool wok[WE];
+  uint32_t woff[WE];
+#pragma unroll
+  for (int e = 0; e < WE; ++e) {
+    const int f = tid + e * kBlock;  // entry: fragment c, k piece wg, fragment row wr16
+    const int c = f >> 6, wg = f & 3, wr16 = (f >> 2) & 15;
+    const int n = n0 + 16 * c + wr16;
+    wok[e] = c < NT && n < N;
+    wr[e] = wt + static_cast<int64_t>(min(n, N - 1)) * ldwt + 8 * wg;
+    woff[e] = static_cast<uint32_t>(min(c, NT - 1) * 1024 + (16 * wg + wr16) * 16);
+  }
+  auto load_w = [&](float (&v)[WE][8], int s) __attribute__((always_inline)) {
+    const int k = 32 * s;
+#pragma unroll
+    for (int e = 0; e < WE; ++e) {
+      const float* p = wr[e] + k;  // (16-B aligned: W^T rows are, and k + 8 wg is a multiple of 8)
+      const int kp = k + 8 * ((tid + e * kBlock) & 3);
+      if (!wok[e]) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[e][q] = 0.f;
+      } else if (s >= SFULL) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[e][q] = (kp + q < K) ? p[q] : 0.f;
+      } else {
+        const float4 lo = *reinterpret_cast<const float4*>(p), hi = *reinterpret_cast<const float4*>(p + 4);
+        v[e][0] = lo.x, v[e][1] = lo.y, v[e][2] = lo.z, v[e][3] = lo.w;
+        v[e][4] = hi.x, v[e][5] = hi.y, v[e][6] = hi.z, v[e][7] = hi.w;
+      }
+    }
+  };
+  auto store_w = [&](const float (&v)[WE][8], int buf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int e = 0; e < WE; ++e) {
+      if (tid + e * kBlock >= NT * kWave) continue;
+      bf16x8 p0, p1, p2;
+      bf3_split(v[e], p0, p1, p2);
+      char* d = lds + buf * BUF + woff[e];
+      *reinterpret_cast<bf16x8*>(d) = p0;
+      *reinterpret_cast<bf16x8*>(d + PLANE) = p1;
+      *reinterpret_cast<bf16x8*>(d + 2 * PLANE) = p2;
+    }
+  };
+
+  f32x4 acc[FR][NT];
+  zero_tile(acc);
+  float xn[FR][8], wn[WE][8];
+  load_x(xn, 0);
+  load_w(wn, 0);
+  store_w(wn, 0);
+  __syncthreads();
+  for (int s = 0; s < S; ++s) {
+    bf16x8 a0[FR], a1[FR], a2[FR];
+#pragma unroll
+    for (int i = 0; i < FR; ++i) bf3_split(xn[i], a0[i], a1[i], a2[i]);
+    const bool more = s + 1 < S;
+    if (more) {
+      load_x(xn, s + 1);
+      load_w(wn, s + 1);
+    }
+    const char* bp = lds + (s & 1) * BUF + lane * 16;
+#pragma unroll
+    for (int c = 0; c < NT; ++c) {
+      const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(bp + c * 1024);
+      const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(bp + PLANE + c * 1024);
+      const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(bp + 2 * PLANE + c * 1024);
+#define GTA_BF3_TERM(A_, B_) \
+  _Pragma("unroll") for (int i = 0; i < FR; ++i) acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A_[i], B_, acc[i][c], 0, 0, 0)
+      GTA_BF3_TERM(a2, b0);
+      GTA_BF3_TERM(a1, b1);
+      GTA_BF3_TERM(a0, b2);
+      GTA_BF3_TERM(a1, b0);
+      GTA_BF3_TERM(a0, b1);
+      GTA_BF3_TERM(a0, b0);
+#undef GTA_BF3_TERM
+    }
+    if (more) store_w(wn, (s + 1) & 1);
+    __syncthreads();
+  }
+  sf_tile(sf, acc);
+  store_tile(acc, out, ldo, M, N, mw, n0, lane, ldo % 4 == 0 && aligned(out, 16));
+}
+
 // Two chained node GEMMs in one pass (GIN's MLP, `vTCAD/GraphOP/genGraphOP.py:103-108`: applynode
 // MM -> SF -> MM -> SF, `template/ISA_defination.yaml:1-31` j,ij->i twice):
 //   out = sf2(bf16(sf1(x W1)) W2), x fp32 [M, K1 <= 128], W1 bf16 [K1, N1 <= 128], W2 bf16 [N1, N2 <= 128].
@@ -6968,13 +7152,15 @@ struct MmArgs {
 // The checks of the three gta_update_mm* entries, in their order; sizes_ok / ptrs_ok carry what an
 // entry adds to the size and pointer conditions.  GTA_OK with M == 0: nothing to do, and the
 // pointers are not looked at.
-int check_mm(const char* who, const MmArgs& a, bool sizes_ok = true, bool ptrs_ok = true) {
+int check_mm(const char* who, const MmArgs& a, bool sizes_ok = true, bool ptrs_ok = true, bool bf3_ok = false) {
   const auto bad = [&](int code, const char* what) { return fail(code, std::string(who) + what); };
   if (a.M < 0 || a.K <= 0 || a.N <= 0 || !sizes_ok) return bad(GTA_ERR_ARG, ": bad sizes");
+  if (a.dtype == GTA_F32_BF16X3 && !bf3_ok) return bad(GTA_ERR_UNSUPPORTED, ": GTA_F32_BF16X3 is gta_update_mm_t's alone");
   if (a.M == 0) return GTA_OK;
   if (!a.x || !a.w || !a.out || !ptrs_ok) return bad(GTA_ERR_ARG, ": bad arguments");
   if (a.K > INT32_MAX || a.N > INT32_MAX) return bad(GTA_ERR_UNSUPPORTED, ": K/N too large");
-  if (a.dtype != GTA_F32 && a.dtype != GTA_BF16 && a.dtype != GTA_F32_BF16) return bad(GTA_ERR_ARG, ": bad dtype");
+  if (a.dtype != GTA_F32 && a.dtype != GTA_BF16 && a.dtype != GTA_F32_BF16 && a.dtype != GTA_F32_BF16X3)
+    return bad(GTA_ERR_ARG, ": bad dtype");
   return GTA_OK;
 }
 }  // namespace
@@ -7164,6 +7350,34 @@ inline bool ring_ok(int dtype, int nt, const void* x, const void* wt, int64_t ld
   return tuning().mm_ring && dtype == GTA_F32 && nt >= 4 && aligned(x, 4) && aligned(wt, 16) && ldwt % 4 == 0;
 }
 
+// k_mm_bf3 over the whole output: one block per (row group, column block), none persistent (a
+// block's only start-up is its first W^T chunk, 16 KB out of L2).  128-row groups (two A fragments
+// per wave: each LDS fragment read feeds twelve MFMAs) once they fill every CU's two block slots;
+// below that 64-row groups, twice the blocks to spread a small M (Cora's 2,708 rows: 43 blocks, not
+// 22).  Both give the same bits.
+int launch_bf3(int nt, int64_t groups, int64_t ncb, hipStream_t s, const MmArgs& a) {
+  if (!aligned(a.x, 4) || !aligned(a.out, 4) || !aligned(a.w, 16) || a.ldw % 4 != 0)
+    return fail(GTA_ERR_UNSUPPORTED, "update_mm_t: GTA_F32_BF16X3 needs 16-B aligned W^T rows (ldwt % 4 == 0)");
+  const int fr = groups * ncb >= 2 * kMmCUs ? 2 : 1;
+  const int64_t blocks = (fr == 2 ? groups : (a.M + 63) / 64) * ncb;
+  if (blocks > INT32_MAX) return fail(GTA_ERR_UNSUPPORTED, "update_mm_t: GTA_F32_BF16X3 grid too large");
+#define GTA_BF3(NT_, FR_)                                                                                          \
+  k_mm_bf3<NT_, FR_><<<dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s>>>(                                 \
+      static_cast<const float*>(a.x), a.ldx, a.row_idx, a.M, static_cast<int>(a.K), static_cast<const float*>(a.w), \
+      a.ldw, static_cast<int>(a.N), a.sf, a.out, a.ldo)
+#define GTA_BF3_F(NT_) if (fr == 2) GTA_BF3(NT_, 2); else GTA_BF3(NT_, 1)
+  switch (nt) {
+    case 1: GTA_BF3_F(1); break;
+    case 2: GTA_BF3_F(2); break;
+    case 4: GTA_BF3_F(4); break;
+    default: GTA_BF3_F(8); break;
+  }
+#undef GTA_BF3_F
+#undef GTA_BF3
+  GTA_LAUNCHED("k_mm_bf3");
+  return GTA_OK;
+}
+
 // K slice of the split form: a multiple of 16 (whole ring stages; k_mm_rows masks a bf16 step's
 // half past the slice end), the same for every kernel form so the forms stay bitwise equal
 inline int64_t mm_kslice(int64_t K, int64_t splits) {
@@ -7176,6 +7390,7 @@ inline int64_t mm_kslice(int64_t K, int64_t splits) {
 int64_t gta_update_mm_t_splits(int64_t M, int64_t K, int64_t N, int dtype, void* stream) {
   const CallTuning ct_(stream);  // the stream's attached knob set decides mm_split, as for the GEMM itself
   if (M < 0 || K <= 0 || N <= 0) return fail(GTA_ERR_ARG, "update_mm_t_splits: bad sizes");
+  if (dtype == GTA_F32_BF16X3) return 1;  // k_mm_bf3 has no split-K form
   if (tuning().mm_split >= 0) return std::max<int64_t>(1, tuning().mm_split);
   const int nt = mm_nt(N);
   const int64_t units = (M + 127) / 128 * ((N + 16 * nt - 1) / (16 * nt));  // 128-row groups x column blocks
@@ -7190,10 +7405,11 @@ int gta_update_mm_t(const void* x, int64_t ldx, const int32_t* row_idx, int64_t 
                     int64_t ldwt, int64_t N, int dtype, int sf, float* out, int64_t ldo, void* stream) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
   const MmArgs a{x, ldx, row_idx, M, K, wt, ldwt, N, dtype, sf, out, ldo};
-  if (const int rc = check_mm("update_mm_t", a, ldwt >= K); rc != GTA_OK || M == 0) return rc;
+  if (const int rc = check_mm("update_mm_t", a, ldwt >= K, true, true); rc != GTA_OK || M == 0) return rc;
   const int nt = mm_nt(N);
   const int64_t groups = (M + 127) / 128;
   const int64_t ncb = (N + 16 * nt - 1) / (16 * nt);
+  if (dtype == GTA_F32_BF16X3) return launch_bf3(nt, groups, ncb, S(stream), a);
   // (mm_ring = 0 selects k_mm_rows, and a forced ring shape (mm_ring_fr) the ring)
   if (dtype == GTA_F32 && tuning().mm_wave && tuning().mm_ring && !tuning().mm_ring_fr && !row_idx && K >= 16 &&
       launch_wave(nt, S(stream), static_cast<const float*>(x), ldx, M, static_cast<int>(K), static_cast<const float*>(wt),

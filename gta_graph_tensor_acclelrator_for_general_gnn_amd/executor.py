@@ -189,7 +189,8 @@ MAX_MATERIALIZE_BYTES = 96 << 30  # refuse to materialise a single edge tensor l
 
 class Executor:
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, dist=None,
-                 softmax_shift=None, gather_dtype=None, multi_reduce=True, multi_reduce_blocked=False):
+                 softmax_shift=None, gather_dtype=None, multi_reduce=True, multi_reduce_blocked=False,
+                 mm_precision=None):
         self.g = opgraph
         # dist (distributed.Comm): node tensors are this rank's row block; gathers are
         # reduce-scattered to it and dst-side scatters all-gather it (distributed.py)
@@ -278,6 +279,13 @@ class Executor:
                              f"not {gather_dtype}")
         self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
         self.gather_casts = 0
+        #   mm_precision: None or "f32" (the default: nothing changes), or "bf16x3" -- every MM whose
+        #   operands are both fp32 after _mm_dtypes (_node_mm, the pushed-down MMs, _node_gemm, the edge /
+        #   gather GEMM) runs as ops.update_mm(precision="bf16x3"): the bf16 MFMA on three-way splits,
+        #   within the fp32 UPDATE bound but not the default's bits.  MMs with bf16 weights are untouched.
+        if mm_precision not in (None, "f32", "bf16x3"):
+            raise ValueError(f"mm_precision: None, 'f32' or 'bf16x3', not {mm_precision!r}")
+        self.mm_precision = None if mm_precision == "f32" else mm_precision
         self._gather_cache = {}  # id(table) -> (table, its version, the bf16 copy): identity checked on use
         #   mm_first: a gather whose only consumer is a narrowing applynode MM is executed as
         #   MM-then-aggregate (sum_e w_e x_src) W == sum_e w_e (x W)_src -- the layer's output
@@ -505,7 +513,7 @@ class Executor:
         def gemm():
             x, w = self._mm_dtypes(v.local, W)
             self._count(x.shape[0] * (x.shape[1] * x.element_size() + w.shape[1] * 4) + w.numel() * w.element_size())
-            return ops.update_mm(x, w, sf=post_sf)
+            return self._mm(x, w, sf=post_sf)
         # keyed on the source table itself, before any widening: a temporary's address is no identity
         return Scat(_memo(self._nmm, (op.idx, post_sf, id(v.local)), v.local, gemm), v.mode, v.fill)
 
@@ -560,12 +568,12 @@ class Executor:
         sibs = [] if post_sf is not None else self._pending_siblings(x, main_idx, W)
         x2, W2 = self._mm_dtypes(x, W)
         if not sibs:
-            out = ops.update_mm(x2, W2, sf=post_sf)
+            out = self._mm(x2, W2, sf=post_sf)
             self._count(x.shape[0] * (x.shape[1] * x.element_size() + W.shape[1] * 4) + W.numel() * W.element_size())
             return out
         Wc = _sibling_cat([W] + [self.tensors[f"w:{o.idx}"] for o in sibs])
         x2, Wc2 = self._mm_dtypes(x, Wc)
-        out = ops.update_mm(x2, Wc2)
+        out = self._mm(x2, Wc2)
         self._count(x.shape[0] * (x.shape[1] * x.element_size() + Wc.shape[1] * 4) + Wc.numel() * Wc.element_size())
         off = W.shape[1]
         for o in sibs:
@@ -792,9 +800,16 @@ class Executor:
         else:
             x, row_idx = self._to_edge_tensor(v), None
         x, W = self._mm_dtypes(x, W)
-        out = ops.update_mm(x, W, row_idx, sf=post_sf, m=self.graph.nnz if row_idx is None else None)
+        out = self._mm(x, W, row_idx, sf=post_sf, m=self.graph.nnz if row_idx is None else None)
         self._count(self.graph.nnz * (x.shape[1] * x.element_size() + W.shape[1] * 4))
         return out
+
+    def _mm(self, x, W, row_idx=None, sf=None, m=None):
+        """ops.update_mm on operands _mm_dtypes has seen: under mm_precision "bf16x3" an fp32 x fp32
+        product takes that precision; bf16 weights keep their route."""
+        if self.mm_precision == "bf16x3" and x.dtype == W.dtype == torch.float32:
+            return ops.update_mm(x, W, row_idx, sf=sf, m=m, precision="bf16x3")
+        return ops.update_mm(x, W, row_idx, sf=sf, m=m)
 
     @staticmethod
     def _mm_dtypes(x, W):
@@ -1555,14 +1570,15 @@ def set_auto_graph(flag):
 
 
 def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=None, gather_dtype=None,
-                multi_reduce_blocked=False):
+                multi_reduce_blocked=False, mm_precision=None):
     """-> a GraphedRun to replay for this call, or None (run eagerly)."""
     if ops.Tuning.attached(torch.cuda.current_stream(graph.device)):
         return None  # a knob set on this stream: every call reads it (gta.h), so no cached graph
     refs = (opgraph, stream, graph, semantics)
     shifted = SOFTMAX_SHIFT if softmax_shift is None else bool(softmax_shift)
     gdt = None if gather_dtype == torch.float32 else gather_dtype
-    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt, bool(multi_reduce_blocked)), id(tensors), ops.knob_state())
+    mmp = None if mm_precision == "f32" else mm_precision
+    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt, bool(multi_reduce_blocked), mmp), id(tensors), ops.knob_state())
     ent = _AUTO_FAST.get(fkey)
     if ent is not None and not (ent.src is tensors and all(a is b for a, b in zip(ent.refs, refs)) and
                                 len(tensors) == len(ent.tensors) and
@@ -1596,7 +1612,8 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_
         before = torch.cuda.memory_reserved(graph.device)
         try:
             ent.run = GraphedRun(opgraph, stream, graph, ent.tensors, semantics, plan_chunk, warmup=1,
-                                 softmax_shift=shifted, gather_dtype=gdt, multi_reduce_blocked=multi_reduce_blocked)
+                                 softmax_shift=shifted, gather_dtype=gdt, multi_reduce_blocked=multi_reduce_blocked,
+                                 mm_precision=mmp)
         except Exception:  # something in this stream is not capturable: stay eager for this key
             ent.failed = True
             torch.cuda.synchronize(graph.device)
@@ -1625,8 +1642,9 @@ def _evict_pools(keep):
 
 
 def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, sync=True, trace=False,
-               softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False):
-    """softmax_shift: Executor.softmax_shift for this call (None: the module's SOFTMAX_SHIFT).
+               softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None):
+    """mm_precision: Executor.mm_precision for this call (None: every MM on its default route).
+    softmax_shift: Executor.softmax_shift for this call (None: the module's SOFTMAX_SHIFT).
     gather_dtype: Executor.gather_dtype for this call (None: tables are gathered as they are).
     multi_reduce_blocked: Executor.multi_reduce_blocked for this call (False: today's routes)."""
     dev = graph.device
@@ -1634,7 +1652,7 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
         clear_auto_graphs()
     if AUTO_GRAPH and not trace and dev.type == "cuda" and graph.nnz <= AUTO_GRAPH_MAX_EDGES:
         gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift, gather_dtype,
-                         multi_reduce_blocked)
+                         multi_reduce_blocked, mm_precision)
         if gr is not None:
             if sync:
                 torch.cuda.synchronize(dev)
@@ -1645,7 +1663,7 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
             ex = gr.executor
             return ExecResult(ex.values, outputs, time.perf_counter() - t0, ex.alg_bytes, ex.launches), ex
     ex = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
-                  gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked)
+                  gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked, mm_precision=mm_precision)
     ex.trace = trace
     sync = sync and dev.type == "cuda"
     if sync:
@@ -1833,7 +1851,7 @@ class GraphedRun:
     place (its version moved) is re-concatenated / re-transposed into them before the next replay."""
 
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, warmup=2,
-                 softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False):
+                 softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None):
         if graph.device.type != "cuda":
             raise RuntimeError("GraphedRun captures device launches: the graph must be on a HIP device")
         self.tensors = tensors
@@ -1842,7 +1860,8 @@ class GraphedRun:
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
                 Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
-                         gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked).run()
+                         gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked,
+                         mm_precision=mm_precision).run()
         torch.cuda.current_stream(graph.device).wait_stream(side)
         torch.cuda.synchronize(graph.device)
         self.cuda_graph = torch.cuda.CUDAGraph()
@@ -1852,7 +1871,7 @@ class GraphedRun:
             with torch.cuda.graph(self.cuda_graph):
                 self.executor = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk,
                                          softmax_shift=softmax_shift, gather_dtype=gather_dtype,
-                                         multi_reduce_blocked=multi_reduce_blocked)
+                                         multi_reduce_blocked=multi_reduce_blocked, mm_precision=mm_precision)
                 self.outputs = self.executor.run()
         finally:
             taken, ops._CAPTURED_WT[:] = list(ops._CAPTURED_WT), []

@@ -1012,11 +1012,21 @@ def apply_node(bin, sf, a, b=None, out=None, b_broadcast_row=False):
     return out
 
 
-def update_mm(x, w, row_idx=None, sf=None, out=None, m=None):
+MM_PRECISIONS = ("f32", "bf16x3")
+
+
+def update_mm(x, w, row_idx=None, sf=None, out=None, m=None, precision="f32"):
     """out[m] = sf(x[r(m)] . w); x/w float32, bfloat16, or float32 x with bfloat16 w (x rounded
     to bf16 on its way into LDS); out float32.
 
-    row_idx: None (r(m) = m, M = x.shape[0]) or int32 [M] of x rows (gather-GEMM)."""
+    row_idx: None (r(m) = m, M = x.shape[0]) or int32 [M] of x rows (gather-GEMM).
+    precision: "f32" (the default: every route as it was), or "bf16x3" -- fp32 x and w only: the
+    product runs on the bf16 MFMA over three-way bf16 splits of both operands (GTA_F32_BF16X3, gta.h:
+    fp32-level accuracy, not GTA_F32's bits), always gta_update_mm_t on W^T, whatever MM_FORM."""
+    if precision not in MM_PRECISIONS:
+        raise ValueError(f"update_mm: precision must be one of {MM_PRECISIONS}, not {precision!r}")
+    if precision == "bf16x3" and not (x.dtype == torch.float32 and w.dtype == torch.float32):
+        raise TypeError("update_mm: precision='bf16x3' takes float32 x and float32 w")
     _need_gpu(x, w, row_idx, out)
     mixed = x.dtype == torch.float32 and w.dtype == torch.bfloat16
     if not mixed and (x.dtype != w.dtype or x.dtype not in (torch.float32, torch.bfloat16)):
@@ -1035,6 +1045,14 @@ def update_mm(x, w, row_idx=None, sf=None, out=None, m=None):
     if out is None:
         out = torch.empty(M, N, dtype=torch.float32, device=x.device)
     ldo = _rows(out, "out")
+    if precision == "bf16x3":
+        wt = _transposed(w)
+        ldwt = _rows(wt, "w^T", wt.dtype)
+        if N == 1:  # one row: its stride is never used; give the kernel the 16-B multiple it checks
+            ldwt = -(-ldwt // 4) * 4
+        check(_L().gta_update_mm_t(_ptr(x), ldx, _ptr(row_idx), M, K, _ptr(wt), ldwt, N,
+                                   _lib.GTA_F32_BF16X3, _sf(sf), _ptr(out), ldo, _stream(x.device)), "update_mm_t")
+        return out
     dt = _lib.GTA_F32_BF16 if mixed else (_lib.GTA_F32 if x.dtype == torch.float32 else _lib.GTA_BF16)
     splits = _mm_splits(M, K, N, dt, x.device) if MM_FORM == "rows" else 1
     if splits > 1:  # few rows: split K over blocks, slices summed in order (deterministic)

@@ -19,7 +19,7 @@ class Layer:
 
     def __init__(self, network, layer, graph, feature, reorder=False, heads=16, candidate=0, tile_start=None,
                  op_array=None, tile_size_list=None, metadata=None, pingpang=True, sinput=False, aggregator="ADD",
-                 stable_softmax=False, gather_dtype=None, multi_reduce_blocked=False):
+                 stable_softmax=False, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None):
         """pingpang / sinput: compile()'s isPingpang / isSinput (code/compiler.py:475-510) for the
         fusion search; the reference's start.py passes its command-line flags through.
         aggregator: the message gathers' reduce function, "ADD" / "MAX" / "MIN" / "MEAN" / "VAR" /
@@ -36,7 +36,12 @@ class Layer:
         and |x| > 448 saturates; the reducers keep the uncast table).
         multi_reduce_blocked: False (the default: nothing changes) or True -- run() sends sibling
         gathers and lone VAR / STD gathers of a source table beyond L2 through one column-blocked
-        gta_reduce_multi_blocked launch (Executor.multi_reduce_blocked)."""
+        gta_reduce_multi_blocked launch (Executor.multi_reduce_blocked).
+        mm_precision: None / "f32" (the default: nothing changes) or "bf16x3" -- run() sends every fp32 x
+        fp32 MM through ops.update_mm(precision="bf16x3") (Executor.mm_precision)."""
+        if mm_precision not in (None, "f32", "bf16x3"):
+            raise ValueError(f"mm_precision: None, 'f32' or 'bf16x3', not {mm_precision!r}")
+        self.mm_precision = None if mm_precision == "f32" else mm_precision
         if gather_dtype not in (None, torch.float32, torch.bfloat16, torch.float8_e4m3fn):
             raise ValueError("gather_dtype: None, torch.float32, torch.bfloat16 or torch.float8_e4m3fn, "
                              f"not {gather_dtype}")
@@ -106,6 +111,8 @@ class Layer:
             opts["gather_dtype"] = self.gather_dtype
         if self.multi_reduce_blocked:
             opts["multi_reduce_blocked"] = True
+        if self.mm_precision is not None:
+            opts["mm_precision"] = self.mm_precision
         res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync,
                                       **opts)
         if model:

@@ -58,7 +58,9 @@ extern "C" {
                               15 (additive): gta_reduce_multi (MEAN / MAX / MIN / VAR / STD in one pass);
                               15 (additive): gta_reduce_multi_blocked (the same, column-blocked);
                               15 (additive): GTA_FP8 gathered tables in gta_aggregate_blocked_x and
-                              gta_gat_aggregate_blocked_x (no new symbol, no signature changes) */
+                              gta_gat_aggregate_blocked_x (no new symbol, no signature changes);
+                              15 (additive): GTA_F32_BF16X3 in gta_update_mm_t (fp32 operands, fp32-level
+                              products on the bf16 MFMA; no new symbol, no signature changes) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -68,8 +70,10 @@ enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 
  * GTA_FP8 (gta_aggregate_blocked_x / gta_gat_aggregate_blocked_x only): OCP e4m3fn, one byte per
  * element -- sign s, exponent e (4 bits), mantissa m (3 bits): +-m 2^-9 for e = 0 (denormals),
  * +-(1 + m/8) 2^(e-7) otherwise, largest value 448; no infinities, codes 0x7f / 0xff are NaN,
- * 0x80 is -0. */
-enum { GTA_F32 = 0, GTA_BF16 = 1, GTA_F32_BF16 = 2, GTA_FP8 = 3 };
+ * 0x80 is -0.
+ * GTA_F32_BF16X3 (gta_update_mm_t only): fp32 x and W, each split into three bf16 pieces inside the
+ * kernel ("Three-way bf16 split" at gta_update_mm_t). */
+enum { GTA_F32 = 0, GTA_BF16 = 1, GTA_F32_BF16 = 2, GTA_FP8 = 3, GTA_F32_BF16X3 = 4 };
 
 /* Scatter direction (reference ISA `scatter` DIRECTION dst/src,
  * template/ISA_defination.yaml:33-44; op ORDER R/C in the op YAML). */
@@ -594,7 +598,31 @@ int gta_update_mm(const void* x, int64_t ldx, const int32_t* row_idx, int64_t M,
  * otherwise k_mm_rows (x fragments straight to registers, wt staged per K chunk).  Both
  * contract k in the same order: bitwise equal to each other, fp32 rounding away from
  * gta_update_mm.  Every form is a hand-written kernel of this library (no vendor GEMM): the
- * result depends only on the shape and the operands, identical in every process. */
+ * result depends only on the shape and the operands, identical in every process.
+ *
+ * Three-way bf16 split (dtype GTA_F32_BF16X3, ABI 15 additive; this entry alone): the operands of the
+ * GTA_F32 call -- fp32 x [*, K] (ldx >= K, rows 4-B aligned), optional row_idx, fp32 wt = W^T [N, K]
+ * with 16-B aligned rows (ldwt % 4 == 0, else GTA_ERR_UNSUPPORTED), fp32 out, any sf, any M, K, N >= 1
+ * -- with fp32-level products on v_mfma_f32_16x16x32_bf16 (k_mm_bf3).  Stateless: no workspace and
+ * no pre-split planes; W^T is split inside the kernel as it is staged.
+ *   Split: every value v of x and of W becomes v0 + v1 + v2 with v0 = RNE_bf16(v), v1 = RNE_bf16(v -
+ *   v0), v2 = RNE_bf16((v - v0) - v1), both subtractions in fp32 (exact).  v0 + v1 + v2 == v for every
+ *   normal fp32 v whose pieces stay in bf16's normal range: the pieces hold all 24 significand bits.
+ *   Products: six of the nine are kept -- x0 w0, x0 w1, x1 w0, x0 w2, x1 w1, x2 w0; x1 w2, x2 w1 and
+ *   x2 w2 (together <= about 3 x 2^-24 |x||w|) are dropped.
+ *   Order: K is walked in 32-k steps, ascending (the K tail is one more step, zeros past K).  Per
+ *   step and output element the six MFMAs add into the one fp32 accumulator smallest terms first:
+ *   x2 w0, x1 w1, x0 w2, x1 w0, x0 w1, x0 w0.  No atomics, no split K: the result depends only on the
+ *   shape and the operands, and a row's result on that row of x alone.
+ *   Accuracy: |d| <= 1e-5 sum|x||w| + 1e-6 against fp64 of the unrounded inputs, the GTA_F32 bound
+ *   (GTA_F32_BF16 rounds x to 8 bits and cannot meet it).  The bits differ from GTA_F32's.
+ *   Special values (these differ from GTA_F32): a NaN element makes its outputs NaN (the rounding
+ *   keeps NaN NaN).  An infinite element has zero residual pieces; its outputs are non-finite, inf
+ *   or NaN unspecified (inf meets the zero residual pieces of the other operand); |v| above bf16's
+ *   largest finite value (about 3.39e38) rounds to inf and behaves likewise.  A residual piece below
+ *   bf16's normal range loses its bits: an absolute error below 2^-126 x 2^-7 x |w| per term.
+ * gta_update_mm, gta_update_mm_t_split and gta_update_mlp refuse GTA_F32_BF16X3
+ * (GTA_ERR_UNSUPPORTED); gta_update_mm_t_splits returns 1 for it. */
 int gta_update_mm_t(const void* x, int64_t ldx, const int32_t* row_idx, int64_t M, int64_t K, const void* wt,
                     int64_t ldwt, int64_t N, int dtype, int sf, float* out, int64_t ldo, void* stream);
 
