@@ -71,7 +71,10 @@ SIGNATURES = {
                                         _vp, _i64, _i64, _vp, _vp]),
     "gta_gat_aggregate_blocked_x": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64,
                                            _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
-    "gta_apply_edge_flat": (_i32, [_i32, _i32, _vp, _vp, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _vp, _i64,
+    "gta_gat_aggregate_blocked_online_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "gta_gat_aggregate_blocked_online": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                                _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "gta_apply_edge_flat": (_i32,[_i32, _i32, _vp, _vp, _i64, _vp, _i32, _i64, _i64, _vp, _i32, _i64, _i64, _vp, _i64,
                                    _vp]),
     "gta_apply_node": (_i32, [_i32, _i32, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i64, _vp]),
     "gta_update_mm": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),

@@ -67,8 +67,9 @@ def parser():
     p.add_argument("--aggregator", default="ADD", type=_aggregator, metavar="{" + ",".join(frontend.AGGREGATORS) + "}",
                    help="reduce function of the message gathers (their COMP_TYPE); GAT takes ADD only.  PNA also "
                         "takes a comma list, e.g. MEAN,MAX,MIN,STD: every aggregator over the same messages, one launch")
-    p.add_argument("--stable-softmax", action="store_true",
-                   help="overflow-safe attention softmax: exp(score - row max) (GAT; off: the unshifted kernels)")
+    p.add_argument("--stable-softmax", nargs="?", const=True, default=False, choices=["online"],
+                   help="overflow-safe attention softmax: exp(score - row max) (GAT; off: the unshifted kernels).  "
+                        "'online': the fused aggregate finds the maximum in its own walk, no shift pass")
     p.add_argument("--gather-dtype", choices=list(GATHER_DTYPES), default="f32",
                    help="storage type of the node tables the column-blocked aggregates gather (bf16 / fp8 = OCP e4m3: "
                         "rounded once, sums in fp32; fp8 is not scaled: values below 2^-10 round to 0, |x| > 448 "

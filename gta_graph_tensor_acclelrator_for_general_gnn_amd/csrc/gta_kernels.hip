@@ -1263,6 +1263,42 @@ __device__ __forceinline__ float sf_shift(int sf, float t, float m) {
   return expf(g - m);
 }
 
+// Online softmax (gta.h, gta_gat_aggregate_blocked_online): the shifted form's outputs with the
+// row maximum found during the item walk itself -- no table, no second walk over the edges.  An
+// item keeps a running maximum m per head (from its first group of edges, never -inf); a group of
+// edges whose largest score gm raises m to m' = red_max(m, gm) first multiplies the accumulators
+// and the head sum by expf(m - m'), then adds its terms expf(s - m').  A group is one step of the
+// item walk: 8 edges in the half-wave and fp8 forms, 4 at F = 64, 2 at F = 256 (fp32 / bf16).
+// expf(0) == 1, so a group that moves no maximum skips the multiply without changing a bit (a
+// wave-uniform vote).  Every product and difference here is its own fp32 operation (never
+// contracted), so the lean and the generic form of one shape agree bitwise.
+__device__ __forceinline__ float online_g(int sf, float t) {  // sf_g, its multiply never fused into s - m
+#pragma clang fp contract(off)
+  return sf_g(sf, t);
+}
+__device__ __forceinline__ float online_w(float g, float m) {  // the term of a score g under the maximum m
+#pragma clang fp contract(off)
+  return expf(g - m);
+}
+// the group's maximum gm meets the running m (first: the item's first group starts it); returns m'
+// and rescales the lane's accumulators and head sum when any lane of the wave moved
+template <int VW>
+__device__ __forceinline__ float online_advance(bool first, float m, float gm, float (&acc)[VW], float& ssum) {
+#pragma clang fp contract(off)
+  const float mo = first ? gm : m;
+  const float mn = red_max(mo, gm);
+  if (__any(!(mn == mo))) {  // NaN counts as moved and reaches every accumulator
+    const float f = expf(mo - mn);
+#pragma unroll
+    for (int q = 0; q < VW; ++q) acc[q] = acc[q] * f;
+    ssum = ssum * f;
+  }
+  return mn;
+}
+// slab row of the online form: F partials, H maxima, H sums -- the maxima and sums of an item in one
+// short run -- rows padded to 16 B
+__host__ __device__ inline int64_t online_lds(int64_t F, int64_t H) { return (F + 2 * H + 3) & ~int64_t{3}; }
+
 // ATT (fused GAT attention, GAT ops 6-12 minus the final SF): the edge weight is
 // not read but computed, v = sf(a[row, h] + b[src, h]) from the two score tables
 // (b gathered like x, from the same column block), and the item's per-head sum of
@@ -1502,12 +1538,14 @@ __device__ __forceinline__ void seg4_walk(const int32_t* indices, const int64_t*
 }
 
 template <int VW, int U, bool WEIGHTED, int NT = 0, bool ATT = false, int SFC = -1, int G = 16, bool SH = false,
-          int ET = E_F32>
+          int ET = E_F32, bool ON = false>
 // NT bit 0: non-temporal index/weight loads, bit 1: slab stores; SFC >= 0: the ATT special function
 // fixed at compile time (-1: att.sf at run time); G = lanes per item (16: four items per wave,
 // 32: two items per wave -- one 512-B row per half-wave instruction at F = 128); SH: the ATT
 // weight is the shifted one, expf(g(a + b) - att.shift[row, h]); ET: the rows' element type (E_FP8: a
-// lane holds VW bytes, G = 16 at every width -- VW = 4, 8, 16 for F = 64, 128, 256)
+// lane holds VW bytes, G = 16 at every width -- VW = 4, 8, 16 for F = 64, 128, 256); ON: the online
+// softmax (ATT, exp-form sf): each lane keeps its head's running maximum, a step of U edges is one
+// group (online_advance), and the slab row is F partials, H maxima, H sums
 __global__ void __launch_bounds__(kBlock)
 k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
            int64_t ldx, const float* __restrict__ w, int64_t ldw, int lph, float* __restrict__ slabs,
@@ -1535,6 +1573,8 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
   if (ATT && len > 0) arow = att.a[static_cast<int64_t>(it.row) * att.lda + head];
   float mrow = 0.f;
   if (ATT && SH && len > 0) mrow = att.shift[static_cast<int64_t>(it.row) * att.H + head];
+  static_assert(!ON || (ATT && !SH), "the online softmax is a form of the unshifted ATT walk");
+  float mrun = 0.f;  // ON: the head's running maximum
   auto ldi = [&](int64_t e) { return (NT & 1) ? __builtin_nontemporal_load(indices + e) : indices[e]; };
   int idxv = (l16 < len) ? ldi(eb + l16) : 0;
   for (int c = 0; c < maxlen; c += G) {
@@ -1552,9 +1592,10 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
           row_load<ET, NQ>(x, ldx, src, col, xv[u]);
           if (ATT) {
             const float sv = arow + att.b[static_cast<int64_t>(src) * att.ldb + head];
-            if (SH) wu[u] = (SFC >= 0) ? sf_shift(SFC, sv, mrow) : sf_shift(att.sf, sv, mrow);
+            if (ON) wu[u] = online_g(SFC >= 0 ? SFC : att.sf, sv);  // the score; its term follows the group's maximum
+            else if (SH) wu[u] = (SFC >= 0) ? sf_shift(SFC, sv, mrow) : sf_shift(att.sf, sv, mrow);
             else wu[u] = (SFC >= 0) ? sf_apply(SFC, sv) : sf_apply(att.sf, sv);
-            ssum += wu[u];
+            if (!ON) ssum += wu[u];
           } else {
             const float* wp = w + (eb + c + s + u) * ldw + head;
             wu[u] = (NT & 1) ? __builtin_nontemporal_load(wp) : *wp;
@@ -1562,7 +1603,18 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
         } else {
 #pragma unroll
           for (int q = 0; q < NQ; ++q) xv[u][q] = Row4<ET>::zero();
-          wu[u] = 0.f;
+          wu[u] = ON ? -__builtin_inff() : 0.f;  // ON: a masked slot's score
+        }
+      }
+      if constexpr (ON) {
+        float gm = wu[0];
+#pragma unroll
+        for (int u = 1; u < U; ++u) gm = red_max(gm, wu[u]);
+        mrun = online_advance(c + s == 0, mrun, gm, acc, ssum);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          wu[u] = (c + s + u < len) ? online_w(wu[u], mrun) : 0.f;
+          ssum += wu[u];
         }
       }
 #pragma unroll
@@ -1579,9 +1631,10 @@ k_agg_seg4(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_it
     idxv = idxn;
   }
   if (len > 0) {
-    const int64_t lds = ATT ? F + ((att.H + 3) & ~3) : F;  // sums padded to 16 B
+    const int64_t lds = ON ? online_lds(F, att.H) : ATT ? F + ((att.H + 3) & ~3) : F;  // sums padded to 16 B
     slab_store<(NT & 2) != 0>(slabs + k * lds + col, acc);
-    if (ATT && l16 % lph == 0) slabs[k * lds + F + head] = ssum;
+    if (ON && l16 % lph == 0) slabs[k * lds + F + head] = mrun;
+    if (ATT && l16 % lph == 0) slabs[k * lds + F + (ON ? att.H : 0) + head] = ssum;
   }
 }
 
@@ -1603,7 +1656,12 @@ __device__ __forceinline__ float quad_bcast(float v) {  // lane (l & ~3) | SEL o
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), SEL * 0x55, 0xF, 0xF, false));
 }
 
-// lane l ^ 4: the neighbouring quad of a 16-lane row.  gfx9 DPP has no row_xmask, so two row
+template <int PERM>
+__device__ __forceinline__ float quad_perm(float v) {  // DPP quad_perm: lane i of each quad reads lane (PERM >> 2i) & 3
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), PERM, 0xF, 0xF, false));
+}
+
+// lane l ^ 4: the neighbouring quad of a 16-lane row. gfx9 DPP has no row_xmask, so two row
 // rotations (row_ror:n -- lane l reads lane (l - n) mod 16 of its row) and a pick by quad parity
 __device__ __forceinline__ float xmask4(float v, bool odd_quad) {
   const float from_lo = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xF, 0xF, false));
@@ -2472,7 +2530,14 @@ k_agg_h32pf(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_i
 // SH: the shifted weight, v = expf(leaky_relu(a + b) - shift[row, h]); the row's shift is loaded
 // once beside a[row, h], the 2-SF step and the direct epilogue are unchanged.
 // BF: bf16 x rows as in k_agg_h32<BF> (the score tables stay fp32).
-template <int NT, bool SH = false, bool BF = false>
+// ON: the online softmax (online_advance), a step's 8 edges one group.  In a full step lane (h, q)
+// holds the scores of edges 2q and 2q+1; their maximum folded over the quad's four lanes by two DPP
+// quad permutes is the head's group maximum (no LDS), then the two terms expf(s - m') per lane and
+// the broadcasts as before.  A tail step evaluates its head's scores per lane, as the generic form
+// does.  Same groups, maxima, rescales and sum order as k_agg_seg4<4, 8, ., ., ATT, ., 32, ., ., ON>:
+// bitwise equal to it.  Slab row k: 128 partials, 8 maxima, 8 sums; the direct epilogue writes the
+// row with factor expf(0) = 1, as k_seg_reduce_att_online would.
+template <int NT, bool SH = false, bool BF = false, bool ON = false>
 __global__ void __launch_bounds__(kBlock)
 k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_items_p, const float* __restrict__ x,
           uint32_t row_bytes, const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
@@ -2480,7 +2545,8 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
           const int64_t* __restrict__ row_ptr = nullptr, int normalize = 1, float* __restrict__ y = nullptr,
           int64_t ldy = 0, float* __restrict__ sums = nullptr, int sf_out = GTA_SF_NONE,
           const float* __restrict__ shift = nullptr) {
-  constexpr int G = 32, U = 8, F = 128, LDS = F + 8;
+  static_assert(!(ON && SH), "the online softmax takes no shift table");
+  constexpr int G = 32, U = 8, F = 128, LDS = ON ? F + 16 : F + 8;
   const int lane = threadIdx.x & (kWave - 1);
   const int l32 = lane & (G - 1);
   const ItemSlot d = item_decode<G>(n_items_p, items, lane);
@@ -2499,11 +2565,13 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
   auto row = [&](int src) { return lean_at<XR>(xb, src, row_bytes, colb); };
   auto score = [&](int src) -> float {
     const float sv = arow + lean_at<float>(bb, src, brow_bytes, hb);
+    if (ON) return online_g(GTA_SF_EXP_LEAKY_RELU, sv);  // the score; its term follows the group's maximum
     return SH ? sf_shift(GTA_SF_EXP_LEAKY_RELU, sv, mrow) : sf_apply(GTA_SF_EXP_LEAKY_RELU, sv);
   };
   const int32_t* ic = indices + it.beg;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   float ssum = 0.f;
+  float mrun = 0.f;  // ON: the head's running maximum
   int idxv = (l32 < len) ? ldi(ic + l32) : 0;
   for (int c = 0; c < maxlen; c += G) {
     const int idxn = (c + G + l32 < len) ? ldi(ic + G + l32) : 0;
@@ -2521,7 +2589,15 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
         }
         const int sa = q == 0 ? src[0] : q == 1 ? src[2] : q == 2 ? src[4] : src[6];
         const int sb = q == 0 ? src[1] : q == 1 ? src[3] : q == 2 ? src[5] : src[7];
-        const float v0 = score(sa), v1 = score(sb);
+        float v0 = score(sa), v1 = score(sb);
+        if constexpr (ON) {  // the head's maximum over the step's 8 edges: a butterfly over the quad (max is exact)
+          float gm = red_max(v0, v1);
+          gm = red_max(gm, quad_perm<0xB1>(gm));  // lane ^ 1
+          gm = red_max(gm, quad_perm<0x4E>(gm));  // lane ^ 2
+          mrun = online_advance(c + s == 0, mrun, gm, acc, ssum);
+          v0 = online_w(v0, mrun);
+          v1 = online_w(v1, mrun);
+        }
         wu[0] = quad_bcast<0>(v0); wu[1] = quad_bcast<0>(v1);
         wu[2] = quad_bcast<1>(v0); wu[3] = quad_bcast<1>(v1);
         wu[4] = quad_bcast<2>(v0); wu[5] = quad_bcast<2>(v1);
@@ -2536,10 +2612,21 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
           if (u < rem) {
             xv[u] = row(src);
             wu[u] = score(src);
-            ssum += wu[u];
+            if (!ON) ssum += wu[u];
           } else {
             xv[u] = Row4<BF>::zero();
-            wu[u] = 0.f;
+            wu[u] = ON ? -__builtin_inff() : 0.f;  // ON: a masked slot's score
+          }
+        }
+        if constexpr (ON) {
+          float gm = wu[0];
+#pragma unroll
+          for (int u = 1; u < U; ++u) gm = red_max(gm, wu[u]);
+          mrun = online_advance(c + s == 0, mrun, gm, acc, ssum);
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            wu[u] = (u < rem) ? online_w(wu[u], mrun) : 0.f;
+            ssum += wu[u];
           }
         }
       }
@@ -2572,7 +2659,8 @@ k_att_h32(const int32_t* __restrict__ indices, const int64_t* __restrict__ n_ite
     }
     float* o = slabs + k * LDS;
     slab_store<(NT & 2) != 0>(o + l32 * 4, acc);
-    if (q == 0) o[F + h] = ssum;
+    if (ON && q == 0) o[F + h] = mrun;
+    if (q == 0) o[F + (ON ? 8 : 0) + h] = ssum;
   }
 }
 
@@ -2787,6 +2875,66 @@ k_seg_reduce_att(int64_t n_rows, const float* __restrict__ slabs, int H, int nor
       const float* ss = slabs + id[u] * lds + F;
       sh += ss[head];
       if (lane < H) sl += ss[lane];
+    }
+  });
+  Vec<VW> o;
+#pragma unroll
+  for (int q = 0; q < VW; ++q) o.v[q] = normalize ? (any ? acc[q] / sh : 0.f) : acc[q];
+  if (sf_out != GTA_SF_NONE) {
+#pragma unroll
+    for (int q = 0; q < VW; ++q) o.v[q] = sf_apply(sf_out, o.v[q]);
+  }
+  o.store(y + row * ldy + col);
+  if (sums != nullptr && lane < H) sums[row * H + lane] = sl;
+}
+
+// Ordered reduce of the online attention form (slab rows of online_lds floats: F partials, H maxima,
+// H sums, each item's relative to its own maximum m_k).  First walk of the row's items: M = max_k m_k
+// per head (red_max: exact, NaN kept) from the H maxima alone -- one short run per item.  Second
+// walk, the same (block, part) order: acc = fmaf(f_k, acc_k, acc) and s = fmaf(f_k, s_k, s) with
+// f_k = expf(m_k - M), which is exactly 1 for the item holding M.  Then k_seg_reduce_att's divide,
+// sf_out, sums and skip_single.  A lane carries its columns' head and, for `sums`, head `lane`.
+template <int VW>
+__global__ void __launch_bounds__(kBlock)
+k_seg_reduce_att_online(int64_t n_rows, const float* __restrict__ slabs, int H, int normalize, float* __restrict__ y,
+                        int64_t ldy, float* __restrict__ sums, RowItems ri, int skip_single, int sf_out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  if (row >= n_rows) return;
+  if (skip_single && ri.row_ptr[row + 1] - ri.row_ptr[row] == 1) return;  // written by its item
+  const int col = lane * VW;
+  constexpr int F = kWave * VW;
+  const int64_t lds = online_lds(F, H);
+  const int head = col / (F / H);
+  const int hl = lane < H ? lane : head;  // the head whose sum this lane reports
+  const bool any = ri.row_ptr[row + 1] > ri.row_ptr[row];
+  float mh = 0.f, ml = 0.f;
+  bool first = true;
+  for_row_items<VW>(ri, row, lane, [&](int64_t i0, int64_t i1, int64_t i2, int64_t i3, int m) {
+    const int64_t id[4] = {i0, i1, i2, i3};
+    for (int u = 0; u < m; ++u) {
+      const float* mm = slabs + id[u] * lds + F;
+      const float a = mm[head], b = mm[hl];
+      mh = first ? a : red_max(mh, a);
+      ml = first ? b : red_max(ml, b);
+      first = false;
+    }
+  });
+  float acc[VW];
+#pragma unroll
+  for (int q = 0; q < VW; ++q) acc[q] = 0.f;
+  float sh = 0.f, sl = 0.f;
+  for_row_items<VW>(ri, row, lane, [&](int64_t i0, int64_t i1, int64_t i2, int64_t i3, int m) {
+    const int64_t id[4] = {i0, i1, i2, i3};
+    for (int u = 0; u < m; ++u) {
+      const float* mm = slabs + id[u] * lds + F;
+      Vec<VW> p;
+      p.load(slabs + id[u] * lds + col);
+      const float fh = online_w(mm[head], mh), fl = online_w(mm[hl], ml);
+#pragma unroll
+      for (int q = 0; q < VW; ++q) acc[q] = fmaf(fh, p.v[q], acc[q]);
+      sh = fmaf(fh, mm[H + head], sh);
+      sl = fmaf(fl, mm[H + hl], sl);
     }
   });
   Vec<VW> o;
@@ -6609,11 +6757,22 @@ int64_t gta_gat_aggregate_blocked_workspace_bytes(int64_t n_rows, int64_t nnz, i
          static_cast<int64_t>(sizeof(float));
 }
 
-// gta_gat_aggregate_blocked (shifted false), gta_gat_aggregate_blocked_shifted and
-// gta_gat_aggregate_blocked_x: one argument check, one dispatch; the fp32 launches are the
+int64_t gta_gat_aggregate_blocked_online_workspace_bytes(int64_t n_rows, int64_t nnz, int64_t blocks, int64_t F,
+                                                         int64_t heads, int64_t item_edges) {
+  if (n_rows < 0 || nnz < 0 || blocks < 1 || blocks > 63 || F <= 0 || heads <= 0 || item_edges < 1)
+    return fail(GTA_ERR_ARG, "gat_online_workspace_bytes: bad sizes");
+  return blocked_max_items(n_rows, nnz, static_cast<int>(blocks), item_edges) * online_lds(F, heads) *
+         static_cast<int64_t>(sizeof(float));
+}
+
+// gta_gat_aggregate_blocked (softmax kPlain), gta_gat_aggregate_blocked_shifted (kShifted),
+// gta_gat_aggregate_blocked_x (either, by its shift) and gta_gat_aggregate_blocked_online (kOnline):
+// one argument check, one dispatch; the fp32 launches are the
 // instantiations they always were, bf16 rows (xv, ldx in bf16 elements) launch their <..., E_BF16> twins;
-// e4m3 rows (GTA_FP8, ldx in bytes) the generic quarter-wave ATT forms at every width.
-static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64_t* indptr, const int32_t* indices,
+// e4m3 rows (GTA_FP8, ldx in bytes) the generic quarter-wave ATT forms at every width.  The online
+// form takes the same shapes through the same table with the kernels' ON parameter set.
+enum GatSoftmax { kPlain = 0, kShifted = 1, kOnline = 2 };
+static int gat_aggregate_blocked_impl(const char* who, GatSoftmax softmax, const int64_t* indptr, const int32_t* indices,
                                       int64_t n_rows, int64_t n_cols, int64_t nnz, const void* xv, int64_t ldx,
                                       int64_t F, int x_dtype, const float* a_dst, int64_t lda, const float* b_src, int64_t ldb,
                                       int64_t heads, int sf, int normalize, int sf_out, float* y, int64_t ldy,
@@ -6628,8 +6787,9 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
   const bool bf = x_dtype == GTA_BF16, f8 = x_dtype == GTA_FP8;
   const unsigned xe = f8 ? 1u : (bf ? 2u : 4u);  // bytes per gathered element
   const float* x = static_cast<const float*>(xv);  // bf16 / fp8 rows: read as such by their kernels only
+  const bool shifted = softmax == kShifted, online = softmax == kOnline;
   if (shifted && !shift) return fail(GTA_ERR_ARG, std::string(who) + ": shift is required");
-  if (shifted && !sf_is_exp_form(sf))
+  if ((shifted || online) && !sf_is_exp_form(sf))
     return fail(GTA_ERR_UNSUPPORTED, std::string(who) + ": sf must be EXP_LEAKY_RELU or EXP");
   if (n_rows == 0) return GTA_OK;
   if (!indptr || !x || !a_dst || !b_src || !y || !plan || (!workspace && nnz > 0))
@@ -6649,11 +6809,12 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
     // the generic G-lane attention form <VW, U, ATT, SFC (elr fixed at compile time), G, SH, ET>; F8: the
     // fp8 shapes (G = 16, VW = F/16 at every width)
     auto seg4 = [&](auto VW, auto U, auto G, dim3 grid, int lanes_per_head, auto F8) {
-      with_bools([&](auto ELR, auto SH, auto BF) {
+      with_bools([&](auto ELR, auto SH, auto BF, auto ON) {
         constexpr int ET = F8() ? E_FP8 : (BF() ? E_BF16 : E_F32);
-        k_agg_seg4<VW(), U(), false, 0, true, (ELR() ? GTA_SF_EXP_LEAKY_RELU : -1), G(), SH(), ET>
-            <<<grid, c.blk, 0, c.s>>>(indices, c.nit, x, ldx, nullptr, 0, lanes_per_head, c.slabs, c.its, att);
-      }, elr, shifted, bf);
+        if constexpr (!(SH() && ON()))
+          k_agg_seg4<VW(), U(), false, 0, true, (ELR() ? GTA_SF_EXP_LEAKY_RELU : -1), G(), SH(), ET, ON()>
+              <<<grid, c.blk, 0, c.s>>>(indices, c.nit, x, ldx, nullptr, 0, lanes_per_head, c.slabs, c.its, att);
+      }, elr, shifted, bf, online);
     };
     constexpr BC<true> fp8{};
     constexpr BC<false> wide{};
@@ -6672,10 +6833,12 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
                           aligned(y, 16);
       skip_single = direct;
       const int64_t* rp = direct ? c.v.row_ptr : nullptr;
-      with_bools([&](auto SH, auto BF) {  // NT bit 2: non-temporal slab stores; shift is NULL unless shifted
-        k_att_h32<2, SH(), BF()><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, a_dst, lda, b_src, bbytes, c.slabs,
-                                                           c.its, rp, normalize, y, ldy, sums, sf_out, shift);
-      }, shifted, bf);
+      with_bools([&](auto SH, auto BF, auto ON) {  // NT bit 2: non-temporal slab stores; shift is NULL unless shifted
+        if constexpr (!(SH() && ON()))
+          k_att_h32<2, SH(), BF(), ON()><<<c.g2h, c.blk, 0, c.s>>>(indices, c.nit, x, rb, a_dst, lda, b_src, bbytes,
+                                                                   c.slabs, c.its, rp, normalize, y, ldy, sums, sf_out,
+                                                                   shift);
+      }, shifted, bf, online);
     } else if (F == 128 && (F / heads) % 4 == 0 && lph32 >= 1 && 32 % lph32 == 0) {
       seg4(IC<4>{}, IC<8>{}, IC<32>{}, c.g2h, lph32, wide);
     } else if (vq == 4) {
@@ -6687,9 +6850,13 @@ static int gat_aggregate_blocked_impl(const char* who, bool shifted, const int64
   }
   const int H = static_cast<int>(heads);
   dispatch_vw(static_cast<int>(F / 64), [&](auto V) {  // skip_single is set at F = 128 only
-    k_seg_reduce_att<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, H, normalize, y, ldy, sums, c.ri, skip_single, sf_out);
+    if (online)
+      k_seg_reduce_att_online<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, H, normalize, y, ldy, sums, c.ri,
+                                                            skip_single, sf_out);
+    else
+      k_seg_reduce_att<V()><<<c.g3, c.blk, 0, c.s>>>(n_rows, c.slabs, H, normalize, y, ldy, sums, c.ri, skip_single, sf_out);
   });
-  GTA_LAUNCHED("k_seg_reduce_att");
+  GTA_LAUNCHED(online ? "k_seg_reduce_att_online" : "k_seg_reduce_att");
   return GTA_OK;
 }
 
@@ -6698,7 +6865,7 @@ int gta_gat_aggregate_blocked(const int64_t* indptr, const int32_t* indices, int
                               const float* b_src, int64_t ldb, int64_t heads, int sf, int normalize, int sf_out,
                               float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks, int64_t item_edges,
                               void* workspace, void* stream) {
-  return gat_aggregate_blocked_impl("gat_aggregate_blocked", false, indptr, indices, n_rows, n_cols, nnz, x, ldx, F,
+  return gat_aggregate_blocked_impl("gat_aggregate_blocked", kPlain, indptr, indices, n_rows, n_cols, nnz, x, ldx, F,
                                     GTA_F32, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums, plan, blocks,
                                     item_edges, workspace, nullptr, stream);
 }
@@ -6709,7 +6876,7 @@ int gta_gat_aggregate_blocked_shifted(const int64_t* indptr, const int32_t* indi
                                       int normalize, int sf_out, float* y, int64_t ldy, float* sums, const void* plan,
                                       int64_t blocks, int64_t item_edges, void* workspace, const float* shift,
                                       void* stream) {
-  return gat_aggregate_blocked_impl("gat_aggregate_blocked_shifted", true, indptr, indices, n_rows, n_cols, nnz, x,
+  return gat_aggregate_blocked_impl("gat_aggregate_blocked_shifted", kShifted, indptr, indices, n_rows, n_cols, nnz, x,
                                     ldx, F, GTA_F32, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums,
                                     plan, blocks, item_edges, workspace, shift, stream);
 }
@@ -6719,9 +6886,20 @@ int gta_gat_aggregate_blocked_x(const int64_t* indptr, const int32_t* indices, i
                                 int64_t lda, const float* b_src, int64_t ldb, int64_t heads, int sf, int normalize,
                                 int sf_out, float* y, int64_t ldy, float* sums, const void* plan, int64_t blocks,
                                 int64_t item_edges, void* workspace, const float* shift, void* stream) {
-  return gat_aggregate_blocked_impl("gat_aggregate_blocked_x", shift != nullptr, indptr, indices, n_rows, n_cols, nnz,
-                                    x, ldx, F, x_dtype, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy,
-                                    sums, plan, blocks, item_edges, workspace, shift, stream);
+  return gat_aggregate_blocked_impl("gat_aggregate_blocked_x", shift != nullptr ? kShifted : kPlain, indptr, indices,
+                                    n_rows, n_cols, nnz, x, ldx, F, x_dtype, a_dst, lda, b_src, ldb, heads, sf, normalize,
+                                    sf_out, y, ldy, sums, plan, blocks, item_edges, workspace, shift, stream);
+}
+
+int gta_gat_aggregate_blocked_online(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                                     int64_t nnz, const void* x, int64_t ldx, int64_t F, int x_dtype,
+                                     const float* a_dst, int64_t lda, const float* b_src, int64_t ldb, int64_t heads,
+                                     int sf, int normalize, int sf_out, float* y, int64_t ldy, float* sums,
+                                     const void* plan, int64_t blocks, int64_t item_edges, void* workspace,
+                                     void* stream) {
+  return gat_aggregate_blocked_impl("gat_aggregate_blocked_online", kOnline, indptr, indices, n_rows, n_cols, nnz, x,
+                                    ldx, F, x_dtype, a_dst, lda, b_src, ldb, heads, sf, normalize, sf_out, y, ldy, sums,
+                                    plan, blocks, item_edges, workspace, nullptr, stream);
 }
 
 }  // extern "C"

@@ -179,8 +179,17 @@ def _mean_scale(g):
 # Executor.softmax_shift's default.  True: a matched softmax chain whose SF is an exp-form (SHIFT_SFS) subtracts
 # its row maximum before the exp (ops.softmax_shift once per chain, then the shifted edge_softmax /
 # gat_aggregate_blocked): no overflow to inf / inf, no 0 / 0 for trained attention scores.  False: the unshifted kernels.
+# "online": the fused attention aggregate finds the maximum during its own walk (ops.gat_aggregate_blocked
+# shift="online": no table, no shift pass); an unfused edge_softmax that something reads keeps the table.
 SOFTMAX_SHIFT = False
 SHIFT_SFS = ("EXP_LEAKY_RELU", "EXP")
+
+
+def _shift_mode(softmax_shift):
+    """Executor.softmax_shift's value for the argument: None -> SOFTMAX_SHIFT, "online" kept, else its bool."""
+    if softmax_shift is None:
+        return SOFTMAX_SHIFT
+    return "online" if isinstance(softmax_shift, str) and softmax_shift == "online" else bool(softmax_shift)
 
 EDGE_EXPR = True  # Executor.edge_expr's default (gta_aggregate_expr for applyedge trees); False: unfused (A/B)
 
@@ -255,7 +264,7 @@ class Executor:
         self._att_state = {}
         #   softmax_shift: the chains' exp-form SFs run overflow-safe (SOFTMAX_SHIFT above); the row-max
         #   table of a chain is built once, on first use, and handed to both of its launches
-        self.softmax_shift = SOFTMAX_SHIFT if softmax_shift is None else bool(softmax_shift)
+        self.softmax_shift = _shift_mode(softmax_shift)
         self._att_shift = {}  # score op A -> Lazy shift table [n, H] (beside _att_state)
         #   gather_dtype: None (the default: nothing changes), or torch.bfloat16 -- the storage type of
         #   the node tables the column-blocked kernels gather.  An fp32 table that a SpMM-form ADD
@@ -700,7 +709,12 @@ class Executor:
         want = not norm and self._pending(G)
         E, n = self.graph.nnz, self.graph.n_rows
         x = self._gather_cast(x)
-        if shift is not None:
+        if self.softmax_shift == "online" and sf in SHIFT_SFS:  # the table stays unbuilt unless an unfused reader forces it
+            y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
+                                                sf_out=sf_out, shift="online")
+            # the scores' rows, and the slab maxima: H floats written and read per item, one item per row at least
+            self._count(self._gather_bytes(E, n, F, xe, heads=H) + n * 4 * H + n * 8 * H)
+        elif shift is not None:
             y, sums = ops.gat_aggregate_blocked(self.graph, x, a, b, sf, normalize=norm, want_sums=want, blocks=B,
                                                 sf_out=sf_out, shift=shift.force())
             self._count(self._gather_bytes(E, n, F, xe, heads=H) + n * 8 * H)  # the scores' and the shift's rows
@@ -1575,7 +1589,7 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_
     if ops.Tuning.attached(torch.cuda.current_stream(graph.device)):
         return None  # a knob set on this stream: every call reads it (gta.h), so no cached graph
     refs = (opgraph, stream, graph, semantics)
-    shifted = SOFTMAX_SHIFT if softmax_shift is None else bool(softmax_shift)
+    shifted = _shift_mode(softmax_shift)
     gdt = None if gather_dtype == torch.float32 else gather_dtype
     mmp = None if mm_precision == "f32" else mm_precision
     fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt, bool(multi_reduce_blocked), mmp), id(tensors), ops.knob_state())

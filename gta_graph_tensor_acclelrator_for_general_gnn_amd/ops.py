@@ -509,6 +509,17 @@ class BlockedPlan:
             self._ws[key] = torch.empty(int(nb), dtype=torch.uint8, device=self.graph.device)
         return self._ws[key]
 
+    def workspace_att_online(self, F, heads):
+        """Partial rows of the online fused attention aggregate ([items, F + 2 heads padded to 4]:
+        partials, per-head maxima, per-head sums)."""
+        key = ("att_online", F, heads)
+        if key not in self._ws:
+            nb = check(_L().gta_gat_aggregate_blocked_online_workspace_bytes(self.graph.n_rows, self.graph.nnz,
+                                                                             self.blocks, F, heads, self.item_edges),
+                       "gat_online_workspace_bytes")
+            self._ws[key] = torch.empty(int(nb), dtype=torch.uint8, device=self.graph.device)
+        return self._ws[key]
+
     @staticmethod
     def supports_att(F, heads):
         """Shapes of gta_gat_aggregate_blocked: F in {64, 128, 256}, (F/heads) a multiple of F/16
@@ -729,9 +740,18 @@ def gat_aggregate_blocked(graph, x, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize
     apply_node(None, sf_out, out).  sums[i, h] = sum_e v (want_sums / sums given).  Returns (out, sums).
     shift: None, or the row-max table of softmax_shift for the same graph, scores and sf: the
     overflow-safe form (gta_gat_aggregate_blocked_shifted), v = exp(g(a + b) - shift[dst]).
+    shift="online": the same outputs with no table and no second walk over the edges
+    (gta_gat_aggregate_blocked_online): every item keeps a running maximum and rescales its
+    accumulators when it moves, the ordered reduce folds the items' maxima.  Within the bound of
+    the shifted form, not bitwise equal to it.
     x: fp32, or bf16 (gta_gat_aggregate_blocked_x, shifted or not: bitwise the call on x.float();
     16-B aligned rows, ldx % 8 == 0), or e4m3 (to_fp8: the same contract; ldx % 16 == 0); the score
     tables, out and sums stay fp32."""
+    online = isinstance(shift, str)
+    if online:
+        if shift != "online":
+            raise ValueError(f"gat_aggregate_blocked: shift must be None, a tensor or 'online', not {shift!r}")
+        shift = None
     _need_gpu(x, a_dst, b_src, out, sums, shift, graph.indptr)
     F, H = x.shape[1], a_dst.shape[1]
     if b_src.shape[1] != H:
@@ -750,17 +770,25 @@ def gat_aggregate_blocked(graph, x, a_dst, b_src, sf="EXP_LEAKY_RELU", normalize
         sums = torch.empty(graph.n_rows, H, dtype=torch.float32, device=x.device)
     if sums is not None and (not sums.is_contiguous() or tuple(sums.shape) != (graph.n_rows, H)):
         raise ValueError("gat_aggregate_blocked: sums must be a contiguous [N, heads] tensor")
-    ws = plan.workspace_att(F, H)
-    if x.dtype in (torch.bfloat16, FP8):
-        f8 = x.dtype == FP8
-        ldx = _fp8_rows(x, "gat_aggregate_blocked") if f8 else _rows(x, "x", torch.bfloat16)
-        if not f8 and (ldx % 8 or x.data_ptr() % 16):
+    ws = plan.workspace_att_online(F, H) if online else plan.workspace_att(F, H)
+    if online or x.dtype in (torch.bfloat16, FP8):
+        f8, bf = x.dtype == FP8, x.dtype == torch.bfloat16
+        ldx = _fp8_rows(x, "gat_aggregate_blocked") if f8 else _rows(x, "x", x.dtype if bf else torch.float32)
+        if bf and (ldx % 8 or x.data_ptr() % 16):
             raise ValueError("gat_aggregate_blocked: a bf16 x needs 16-B aligned rows (ldx % 8 == 0)")
+        x_dtype = _lib.GTA_FP8 if f8 else (_lib.GTA_BF16 if bf else _lib.GTA_F32)
+        if online:
+            check(_L().gta_gat_aggregate_blocked_online(
+                _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols, graph.nnz, _ptr(x), ldx, F,
+                x_dtype, _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"), H, _sf(sf),
+                1 if normalize else 0, _sf(sf_out), _ptr(out), _rows(out, "out"), _ptr(sums), _ptr(plan.buf), plan.blocks,
+                plan.item_edges, _ptr(ws), _stream(x.device)), "gat_aggregate_blocked_online")
+            return out, sums
         if shift is not None:
             _shift_table(graph, shift, H, "gat_aggregate_blocked")
         check(_L().gta_gat_aggregate_blocked_x(
             _ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.n_cols, graph.nnz, _ptr(x), ldx, F,
-            _lib.GTA_FP8 if f8 else _lib.GTA_BF16, _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"),
+            x_dtype, _ptr(a_dst), _rows(a_dst, "a_dst"), _ptr(b_src), _rows(b_src, "b_src"),
             H, _sf(sf), 1 if normalize else 0, _sf(sf_out), _ptr(out), _rows(out, "out"), _ptr(sums), _ptr(plan.buf), plan.blocks,
             plan.item_edges, _ptr(ws), _ptr(shift), _stream(x.device)), "gat_aggregate_blocked_x")
         return out, sums

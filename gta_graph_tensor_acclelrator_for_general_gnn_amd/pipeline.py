@@ -29,7 +29,8 @@ class Layer:
         search returns some 3e5 candidate partitions for such a graph at Cora's size, so a tuple
         aggregator skips it and takes _default_partition() unless op_array is passed.
         stable_softmax: run() evaluates the layer's softmax chains overflow-safe, exp(s - row max)
-        (Executor.softmax_shift); off, the default, is the unshifted path.
+        (Executor.softmax_shift); off, the default, is the unshifted path.  "online": the same,
+        with the fused attention aggregate finding the maximum in its own walk (no shift pass).
         gather_dtype: None (the default: nothing changes) or torch.bfloat16 -- run() stores the node
         tables its column-blocked aggregates gather as bf16 (Executor.gather_dtype) -- or
         torch.float8_e4m3fn: as OCP e4m3 (ops.to_fp8; no scaling, so values below 2^-10 round to 0
@@ -49,7 +50,8 @@ class Layer:
         self.network, self.layer, self.reorder = network, layer, reorder
         multi = isinstance(aggregator, (tuple, list))
         self.aggregator = tuple(aggregator) if multi else aggregator
-        self.stable_softmax = bool(stable_softmax)
+        self.stable_softmax = "online" if isinstance(stable_softmax, str) and stable_softmax == "online" \
+            else bool(stable_softmax)
         self.multi_reduce_blocked = bool(multi_reduce_blocked)
         self.graph = graph
         self.records = frontend.gen_ops(network, layer, graph.n_rows, graph.nnz, feature, reorder, heads, aggregator)
@@ -106,7 +108,7 @@ class Layer:
         only); a multi-layer forward synchronises once at its end instead of twice per layer."""
         opts = {}  # only what is switched on: the default call is the one it always was
         if self.stable_softmax:
-            opts["softmax_shift"] = True
+            opts["softmax_shift"] = self.stable_softmax  # True or "online"
         if self.gather_dtype is not None:
             opts["gather_dtype"] = self.gather_dtype
         if self.multi_reduce_blocked:

@@ -60,7 +60,10 @@ extern "C" {
                               15 (additive): GTA_FP8 gathered tables in gta_aggregate_blocked_x and
                               gta_gat_aggregate_blocked_x (no new symbol, no signature changes);
                               15 (additive): GTA_F32_BF16X3 in gta_update_mm_t (fp32 operands, fp32-level
-                              products on the bf16 MFMA; no new symbol, no signature changes) */
+                              products on the bf16 MFMA; no new symbol, no signature changes);
+                              15 (additive): online softmax in the fused GAT aggregate
+                              (gta_gat_aggregate_blocked_online and its workspace size; no existing
+                              signature changes) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -549,6 +552,45 @@ int gta_gat_aggregate_blocked_shifted(const int64_t* indptr, const int32_t* indi
                                       int normalize, int sf_out, float* y, int64_t ldy, float* sums, const void* plan,
                                       int64_t blocks, int64_t item_edges, void* workspace, const float* shift,
                                       void* stream);
+
+/* ---- Online (overflow-safe, single-walk) fused GAT aggregate, ABI 15 additive ----
+ * gta_gat_aggregate_blocked_online takes the arguments of gta_gat_aggregate_blocked_x without
+ * `shift` and DEFINES its outputs as the shifted form's, with s(e, h) as above and
+ * M(i, h) = max_e s(e, h):  sums[i, h] = sum_e exp(s - M);  normalized y = sum_e exp(s - M) x[src] /
+ * sums;  un-normalized y = sum_e exp(s - M) x[src];  sf_out as in the other forms;  rows without
+ * edges get sf_out(0) and sums 0, decided from their item count.  No table is built and no edge is
+ * walked twice: the maximum is found during the fused walk itself, so the results are within the
+ * project's bound of the fp64 value and NOT bitwise equal to gta_gat_aggregate_blocked_shifted.
+ *   item     Each plan item keeps a running maximum m per head, started by its first group of edges
+ *            (never -inf, so no inf - inf).  A group is one step of the item walk, which fixes the
+ *            result bits: 8 edges at F = 128 and for e4m3 rows at every F, 4 edges at F = 64 and 2
+ *            at F = 256 for fp32 / bf16 rows.  With gm the group's largest score and
+ *            m' = max(m, gm), the per-column accumulators and the per-head sum are multiplied by
+ *            expf(m - m') and then the group's terms expf(s - m') are added (fma per column, in
+ *            edge order).  expf(0) == 1, so the multiply is skipped where no maximum moved.  Masked
+ *            tail slots carry score -inf and weight 0.
+ *   slab     Item k's workspace row holds its F partials, H maxima and H sums, all relative to its
+ *            own m_k; rows are padded to 16 B (gta_gat_aggregate_blocked_online_workspace_bytes;
+ *            the plan is gta_aggregate_blocked_plan_build's).
+ *   reduce   Per row, M = max_k m_k over its items (exact: gta_softmax_shift's entry up to the sign
+ *            of a zero), then in the plan's (block, part) order acc = fma(expf(m_k - M), acc_k, acc)
+ *            and s = fma(expf(m_k - M), s_k, s).  No atomics, fixed order: two calls are bitwise
+ *            equal; plan, blocks and item_edges move the result only through fp32 rounding.
+ *   bounds   The edge holding an item's maximum has weight exactly 1.0f and the item holding M the
+ *            factor exactly 1.0f, so every item sum and every non-empty row's sums is >= 1: no call
+ *            produces inf, 0 / 0 or a NaN that is not in its inputs.  NaN propagates through the
+ *            compare-select maximum: a NaN score makes its (row, head)'s outputs NaN.  Infinite
+ *            scores: unspecified.
+ * sf other than GTA_SF_EXP_LEAKY_RELU / GTA_SF_EXP: GTA_ERR_UNSUPPORTED.  x_dtype, shapes, alignment
+ * and the remaining checks are gta_gat_aggregate_blocked_x's; the score tables stay fp32. */
+int64_t gta_gat_aggregate_blocked_online_workspace_bytes(int64_t n_rows, int64_t nnz, int64_t blocks, int64_t F,
+                                                         int64_t heads, int64_t item_edges);
+int gta_gat_aggregate_blocked_online(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                                     int64_t nnz, const void* x, int64_t ldx, int64_t F, int x_dtype,
+                                     const float* a_dst, int64_t lda, const float* b_src, int64_t ldb, int64_t heads,
+                                     int sf, int normalize, int sf_out, float* y, int64_t ldy, float* sums,
+                                     const void* plan, int64_t blocks, int64_t item_edges, void* workspace,
+                                     void* stream);
 
 /* ---- K3 APPLYEDGE element-wise -----------------------------------------
  * out[e, c] = sf( a[ia(e), c_a] (bin) b[ib(e), c_b] )   for c < max(Fa, Fb)

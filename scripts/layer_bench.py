@@ -78,12 +78,16 @@ def main(names=None, reps=5, trace=False, graphed=False, gather_dtype=None):
 
 if __name__ == "__main__":
     from gta_graph_tensor_acclelrator_for_general_gnn_amd import ops
+    online = False
+    if "--stable-softmax" in sys.argv[1:-1] and sys.argv[sys.argv.index("--stable-softmax") + 1] == "online":
+        del sys.argv[sys.argv.index("--stable-softmax") + 1]  # --stable-softmax online: no shift pass in a fused layer
+        online = True
     argv = [a for a in sys.argv[1:] if a not in ("--trace", "--hipgraph", "--no-mlp", "--graph-all", "--no-bf16-sum",
                                                  "--no-edge-flat", "--no-edge-expr", "--stable-softmax", "--no-auto-graph")]
     if "--no-auto-graph" in sys.argv[1:]:  # every forward through the executor itself (its host time included), no replay
         executor.set_auto_graph(False)
     if "--stable-softmax" in sys.argv[1:]:  # the GAT softmax chains shifted by their row maxima (A/B of the shift pass)
-        executor.SOFTMAX_SHIFT = True
+        executor.SOFTMAX_SHIFT = "online" if online else True
     if "--no-edge-expr" in sys.argv[1:]:  # the applyedge trees of DGN / PNA unfused (A/B of gta_aggregate_expr, ABI 14)
         executor.EDGE_EXPR = False
     if "--no-edge-flat" in sys.argv[1:]:  # apply_edge on the row-sweep forms (A/B of gta_apply_edge_flat, ABI 13)
