@@ -3340,6 +3340,195 @@ __global__ void k_items_permute(BlockedView v) {
   v.row_items[v.item_slot[id]] = nid;
 }
 
+// ---------------------------------------------------------------------------
+// K6/K7/K2 aggregate of e4m3 rows (GTA_FP8), row-chunked: k_agg_rows_f8.
+//   For narrow rows the gather is bound by line requests, not bytes: 100 e4m3 columns
+//   at a 128-B pitch are ONE line per gathered row where the bf16 row takes two.
+//   One wave per work item (k_aggregate's: a row, or a <= chunk slice).  LPR lanes cover a row,
+//   the smallest power of two >= ceil(F / 16); lane cl of an edge slot owns columns 16 cl .. 16 cl +
+//   15 and loads them with one 16-B load (a piece starting at or past column F is never
+//   requested); EPI = 64 / LPR slots share a wave instruction, UR of them are issued before any is
+//   consumed (64 B of rows per lane: k_aggregate's rule; LPR 1 / 2 one block of 64 edges at most).
+//   Indices (and one weight per edge) arrive 64 per coalesced load, the next 64 prefetched, and are
+//   broadcast to the slot's lanes.  Every code widens exactly (v_cvt_pk_f32_fp8), sums are fp32:
+//   slot s takes edges s, s + EPI, ... in order; a tail slot past the item's end loads nothing and
+//   adds w = 0 times x = 0.
+//   Fold across the slots by recursive halving: at lane distance LPR, 2 LPR, ... a lane keeps one
+//   half of the columns it still holds and sends the other (8 + 4 + 2 + 1 exchanges instead of the
+//   butterfly's 16 per stage); with one column left the remaining stages are xor-adds.  Each
+//   column's sum ends in one known lane (its M = 16 >> stages columns start at 16 cl + the slot
+//   bits' offsets), so the epilogue -- k_aggregate's: row_scale, accumulate, the self term with each
+//   product rounded, an fp32 or RNE bf16 y, or a split item's fp32 partial for k_aggregate_combine --
+//   runs on all lanes, for columns < F only.  The order is fixed: two calls are bitwise equal.
+//   xs (the self term) holds bf16 rows: the node's own feature stays at the table's precision.
+// ---------------------------------------------------------------------------
+constexpr int f8_log2(int v) { return v <= 1 ? 0 : 1 + f8_log2(v >> 1); }
+
+// M consecutive values from p on (n < M of them inside the row, or rows not aligned to M: one by one)
+template <int M>
+__device__ __forceinline__ void f8_put(float* p, const float* v, int n, bool vec = true) {
+  if (n == M && vec) {
+    if constexpr (M == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    else if constexpr (M == 2) *reinterpret_cast<float2*>(p) = make_float2(v[0], v[1]);
+    else *p = v[0];
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+    if (i < n) p[i] = v[i];
+}
+template <int M>
+__device__ __forceinline__ void f8_put_bf16(uint16_t* p, const float* v, int n) {
+  uint16_t b[M];
+#pragma unroll
+  for (int i = 0; i < M; ++i) b[i] = to_bf16_bits(v[i]);
+  if (n == M) {
+    if constexpr (M == 4)
+      *reinterpret_cast<uint2*>(p) = make_uint2(b[0] | static_cast<uint32_t>(b[1]) << 16, b[2] | static_cast<uint32_t>(b[3]) << 16);
+    else if constexpr (M == 2) *reinterpret_cast<uint32_t*>(p) = b[0] | static_cast<uint32_t>(b[1]) << 16;
+    else *p = b[0];
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+    if (i < n) p[i] = b[i];
+}
+
+// one halving stage over 2 H held values: the lane whose `dist` bit is set keeps the upper H and sends
+// the lower H to its partner, and the other way round; a[0 .. H) = the kept half + the partner's.
+// Returns the kept half's column offset.  (lo / hi are values before the selects: a select between
+// two elements of a[] turns into a run-time register index)
+template <int H>
+__device__ __forceinline__ int f8_halve(float (&a)[16], int lane, int dist) {
+  const bool up = (lane & dist) != 0;
+  float lo[H], hi[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) { lo[i] = a[i]; hi[i] = a[i + H]; }
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    const float send = up ? lo[i] : hi[i];
+    const float keep = up ? hi[i] : lo[i];
+    a[i] = keep + __shfl_xor(send, dist);
+  }
+  return up ? H : 0;
+}
+
+template <int LPR, int WMODE>
+__global__ void __launch_bounds__(kBlock)
+k_agg_rows_f8(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices, int64_t n_rows, PlanView plan,
+              int use_plan, int x_is_row, const uint8_t* __restrict__ x, int64_t ldx, int F,
+              const float* __restrict__ w, int64_t ldw, int gsz, const float* __restrict__ row_scale,
+              float* __restrict__ y, int64_t ldy, int accumulate, float* __restrict__ partial,
+              const uint16_t* __restrict__ xs, int64_t ldxs, const float* __restrict__ self_scale, int y_bf16) {
+  constexpr int EPI = kWave / LPR;          // edge slots per wave instruction
+  constexpr int UR = LPR < 4 ? LPR : 4;     // 16-B row loads in flight per lane
+  constexpr int STEP = UR * EPI;            // edges per unrolled step (<= 64 at LPR 1 / 2)
+  constexpr int NST = f8_log2(EPI);         // fold stages
+  constexpr int NH = NST < 4 ? NST : 4;     // of them halving
+  constexpr int M = 16 >> NH;               // columns a lane owns after the fold
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t item = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  const int64_t n_items = use_plan ? plan.hdr[0] : n_rows;
+  if (item >= n_items) return;
+
+  const auto [row, eb, ee, split] = work_item(indptr, plan, use_plan, item);
+  const int sub = lane / LPR, cl = lane % LPR;
+  const bool pv = 16 * cl < F;  // this lane's piece starts inside the row
+  const int hcol = (WMODE == WM_HEAD && pv) ? 16 * cl / gsz : 0;
+  float acc[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc[k] = 0.f;
+
+  const bool use_idx = !x_is_row;
+  int idxv = 0;
+  float wv = 0.f;
+  if (use_idx && eb < ee) idxv = indices[min(eb + lane, ee - 1)];
+  if (WMODE == WM_EDGE1 && eb < ee) wv = w[min(eb + lane, ee - 1) * ldw];
+  for (int64_t e0 = eb; e0 < ee; e0 += kWave) {
+    const int n = static_cast<int>(min<int64_t>(kWave, ee - e0));
+    int idxn = 0;
+    float wn = 0.f;
+    if (use_idx) idxn = indices[min(e0 + kWave + lane, ee - 1)];
+    if (WMODE == WM_EDGE1) wn = w[min(e0 + kWave + lane, ee - 1) * ldw];
+    for (int s = 0; s < n; s += STEP) {
+      uint4 r[UR];
+      float wh[UR];
+      int64_t sr[UR];
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {  // the broadcasts first: every row address is known before a load is issued
+        const int j = s + u * EPI + sub;
+        const int jj = j < n ? j : n - 1;
+        const int si = __shfl(idxv, jj);  // (unconditional: no branch between the step's broadcasts)
+        sr[u] = use_idx ? static_cast<int64_t>(si) : row;
+        wh[u] = 0.f;
+        if (WMODE == WM_EDGE1) {
+          const float we = __shfl(wv, jj);
+          wh[u] = j < n ? we : 0.f;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {
+        const int j = s + u * EPI + sub;
+        r[u] = make_uint4(0u, 0u, 0u, 0u);
+        if (j < n && pv) {
+          r[u] = *reinterpret_cast<const uint4*>(x + sr[u] * ldx + 16 * cl);
+          if (WMODE == WM_HEAD) wh[u] = w[(e0 + j) * ldw + hcol];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UR; ++u) {
+        const uint32_t d[4] = {r[u].x, r[u].y, r[u].z, r[u].w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 f = row4_f32(d[q]);
+          const float t[4] = {f.x, f.y, f.z, f.w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            acc[4 * q + k] = (WMODE == WM_NONE) ? acc[4 * q + k] + t[k] : fmaf(wh[u], t[k], acc[4 * q + k]);
+        }
+      }
+    }
+    idxv = idxn;
+    wv = wn;
+  }
+
+  // recursive halving over the slots: stage t pairs lanes LPR << t apart; the lane whose bit is set
+  // keeps the upper half of the columns it holds
+  int off = 0;
+  if constexpr (NST >= 1) off += f8_halve<8>(acc, lane, LPR);
+  if constexpr (NST >= 2) off += f8_halve<4>(acc, lane, LPR << 1);
+  if constexpr (NST >= 3) off += f8_halve<2>(acc, lane, LPR << 2);
+  if constexpr (NST >= 4) off += f8_halve<1>(acc, lane, LPR << 3);
+  if constexpr (NST >= 5) acc[0] += __shfl_xor(acc[0], LPR << 4);
+  if constexpr (NST >= 6) acc[0] += __shfl_xor(acc[0], LPR << 5);
+  const int c = 16 * cl + off;
+  if (c >= F || (NST > 4 && (sub >> 4) != 0)) return;  // (after xor-adds the upper slots hold copies)
+  const int nc = min(M, F - c);
+  if (split) {
+    f8_put<M>(partial + item * static_cast<int64_t>(F) + c, acc, nc, F % M == 0);
+    return;
+  }
+  const float scale = row_scale != nullptr ? row_scale[row] : 1.f;
+  float o[M];
+  if (accumulate) {
+    const float* yp = y + row * ldy + c;
+#pragma unroll
+    for (int i = 0; i < M; ++i) o[i] = (i < nc ? yp[i] : 0.f) + scale * acc[i];
+  } else if (xs != nullptr) {
+#pragma clang fp contract(off)
+    // no fma contraction: each product rounded, as the unfused MUL and aggregate store them
+    const uint16_t* sp = xs + row * ldxs + c;
+    const float ss = self_scale ? *self_scale : 1.f;
+#pragma unroll
+    for (int i = 0; i < M; ++i) o[i] = (i < nc ? load_elem(sp + i) : 0.f) * ss + scale * acc[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < M; ++i) o[i] = scale * acc[i];
+  }
+  if (y_bf16) f8_put_bf16<M>(reinterpret_cast<uint16_t*>(y) + row * ldy + c, o, nc);
+  else f8_put<M>(y + row * ldy + c, o, nc);
+}
+
 // sum the chunk partials of split rows, in chunk order
 __global__ void __launch_bounds__(kBlock)
 k_aggregate_combine(PlanView plan, int F, const float* __restrict__ row_scale, float* __restrict__ y, int64_t ldy,
@@ -5897,11 +6086,76 @@ bool launch_combine(int64_t nnz, int64_t plan_chunk, Launch launch) {
   return sb > 0;
 }
 
+template <int LPR>
+void launch_rows_f8(int wm, const AggArgs& a, int64_t n_items_bound, hipStream_t s) {
+  const dim3 grid = row_grid(n_items_bound), blk(kBlock);
+#define GTA_ROWS_F8(WM_)                                                                                            \
+  k_agg_rows_f8<LPR, WM_><<<grid, blk, 0, s>>>(a.indptr, a.indices, a.n_rows, a.plan, a.use_plan, a.x_is_row,      \
+                                               static_cast<const uint8_t*>(a.x), a.ldx, a.F, a.w, a.ldw, a.gsz,   \
+                                               a.row_scale, a.y, a.ldy, a.accumulate, a.partial,                   \
+                                               static_cast<const uint16_t*>(a.xs), a.ldxs, a.self_scale, a.y_bf16)
+  if (wm == WM_NONE) GTA_ROWS_F8(WM_NONE); else if (wm == WM_EDGE1) GTA_ROWS_F8(WM_EDGE1); else GTA_ROWS_F8(WM_HEAD);
+#undef GTA_ROWS_F8
+}
+
+// gta_aggregate / gta_aggregate_self over e4m3 rows (GTA_FP8; aggregate_impl has checked the sizes,
+// x_mode and the self-term / bf16-y rules): the layouts k_agg_rows_f8 takes, refused before any
+// device work otherwise.  ldx in bytes; xs (the self term) bf16 rows, ldxs in bf16 elements
+int aggregate_rows_f8(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
+                      const void* x, int64_t ldx, int64_t F, const float* w, int64_t ldw, int64_t heads,
+                      const float* row_scale, float* y, int64_t ldy, int accumulate, const void* plan,
+                      int64_t plan_chunk, void* workspace, void* stream, const void* xs, int64_t ldxs,
+                      const float* self_scale, int y_bf16) {
+  if (x_mode == GTA_IDX_EDGE || (w && heads == F))
+    return fail(GTA_ERR_UNSUPPORTED, "aggregate: fp8 rows are gathered by index (SRC / DST) with head weights or none");
+  if (F > 256) return fail(GTA_ERR_UNSUPPORTED, "aggregate: fp8 rows of at most 256 columns");
+  if (w && (heads <= 0 || F % heads != 0)) return fail(GTA_ERR_ARG, "aggregate: heads must divide F");
+  if (w && heads > 1 && (F / heads) % 16)
+    return fail(GTA_ERR_UNSUPPORTED, "aggregate: fp8 rows take head weights over a multiple of 16 columns");
+  const int64_t pieces = (F + 15) / 16;
+  if (nnz > 0 && (!aligned(x, 16) || ldx % 16 || ldx < 16 * pieces))
+    return fail(GTA_ERR_UNSUPPORTED, "aggregate: an fp8 x needs 16-B aligned rows of whole 16-B pieces (ldx in bytes)");
+  if (!aligned(y, 16) || ldy % (y_bf16 ? 8 : 4))
+    return fail(GTA_ERR_UNSUPPORTED, "aggregate: with an fp8 x, y needs 16-B aligned rows");
+  if (ldy < F) return fail(GTA_ERR_ARG, "aggregate: ldy >= F");
+  if (xs && (!aligned(xs, 16) || ldxs % 8))
+    return fail(GTA_ERR_UNSUPPORTED, "aggregate_self: with an fp8 x, x_self holds bf16 rows, 16-B aligned");
+  if (n_rows == 0) return GTA_OK;
+  if (!indptr || !y || (nnz > 0 && !x)) return fail(GTA_ERR_ARG, "aggregate: bad arguments");
+  if (x_mode == GTA_IDX_SRC && !indices && nnz > 0) return fail(GTA_ERR_ARG, "aggregate: x_mode SRC needs indices");
+  if (nnz == 0) {
+    x = y;  // any valid address: no row has an edge to read
+    w = nullptr;
+  }
+  AggArgs a{};
+  const int64_t bound = gather_args(a, "aggregate", indptr, indices, n_rows, nnz, x_mode, x, ldx, F, y, ldy, plan,
+                                    plan_chunk, workspace);
+  if (bound < 0) return static_cast<int>(bound);
+  const int wm = !w ? WM_NONE : (heads == 1 ? WM_EDGE1 : WM_HEAD);
+  a.w = w; a.ldw = ldw; a.gsz = w ? static_cast<int>(F / heads) : 1; a.row_scale = row_scale; a.accumulate = accumulate;
+  a.xs = xs; a.ldxs = ldxs; a.self_scale = self_scale; a.y_bf16 = y_bf16;
+  hipStream_t s = S(stream);
+  if (pieces <= 1) launch_rows_f8<1>(wm, a, bound, s);
+  else if (pieces <= 2) launch_rows_f8<2>(wm, a, bound, s);
+  else if (pieces <= 4) launch_rows_f8<4>(wm, a, bound, s);
+  else if (pieces <= 8) launch_rows_f8<8>(wm, a, bound, s);
+  else launch_rows_f8<16>(wm, a, bound, s);
+  GTA_LAUNCHED("k_agg_rows_f8");
+  const bool combined = plan && launch_combine(nnz, plan_chunk, [&](dim3 grid) {
+    k_aggregate_combine<<<grid, dim3(kBlock), 0, s>>>(a.plan, a.F, row_scale, y, ldy, accumulate, a.partial, xs, ldxs, 1,
+                                                      self_scale, y_bf16);
+  });
+  if (combined) GTA_LAUNCHED("k_aggregate_combine");
+  return GTA_OK;
+}
+
+// f8_ok: the entry point takes e4m3 rows (gta_aggregate, gta_aggregate_self; gta_reduce's ADD does not)
 int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
                    const void* x, int64_t ldx, int64_t F, int x_dtype, const float* w, int64_t ldw, int64_t heads,
                    const float* row_scale, float* y, int64_t ldy, int accumulate, const void* plan,
                    int64_t plan_chunk, void* workspace, void* stream, const void* xs, int64_t ldxs,
-                   const float* self_scale, int y_bf16 = 0, const ExprArgs* ex = nullptr, int ex_mode = 0) {
+                   const float* self_scale, int y_bf16 = 0, const ExprArgs* ex = nullptr, int ex_mode = 0,
+                   bool f8_ok = false) {
   const CallTuning ct_(stream);  // knobs attached to this stream, if any (gta_tuning_attach)
   if (n_rows < 0 || nnz < 0 || F <= 0) return fail(GTA_ERR_ARG, "aggregate: bad sizes");
   ExprArgs exa{};
@@ -5920,6 +6174,9 @@ int aggregate_impl(const int64_t* indptr, const int32_t* indices, int64_t n_rows
   if (xs && (accumulate || ldxs < F)) return fail(GTA_ERR_ARG, "aggregate_self: no accumulate; ld_self >= F");
   if (x_mode != GTA_IDX_EDGE && x_mode != GTA_IDX_SRC && x_mode != GTA_IDX_DST)
     return fail(GTA_ERR_ARG, "aggregate: bad x_mode");
+  if (x_dtype == GTA_FP8 && f8_ok && !ex)
+    return aggregate_rows_f8(indptr, indices, n_rows, nnz, x_mode, x, ldx, F, w, ldw, heads, row_scale, y, ldy, accumulate,
+                             plan, plan_chunk, workspace, stream, xs, ldxs, self_scale, y_bf16);
   if (x_dtype != GTA_F32 && x_dtype != GTA_BF16) return fail(GTA_ERR_ARG, "aggregate: x_dtype must be F32 or BF16");
   const bool bf = x_dtype == GTA_BF16;
   const int xe = bf ? 2 : 4;  // bytes per x element
@@ -6296,7 +6553,7 @@ int gta_aggregate(const int64_t* indptr, const int32_t* indices, int64_t n_rows,
                   const float* row_scale, float* y, int64_t ldy, int accumulate, const void* plan,
                   int64_t plan_chunk, void* workspace, void* stream) {
   return aggregate_impl(indptr, indices, n_rows, nnz, x_mode, x, ldx, F, x_dtype, w, ldw, heads, row_scale, y, ldy,
-                        accumulate, plan, plan_chunk, workspace, stream, nullptr, 0, nullptr);
+                        accumulate, plan, plan_chunk, workspace, stream, nullptr, 0, nullptr, 0, nullptr, 0, /*f8_ok=*/true);
 }
 
 int gta_reduce(int red, const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
@@ -6361,7 +6618,7 @@ int gta_aggregate_self(const int64_t* indptr, const int32_t* indices, int64_t n_
   if (y_dtype != GTA_F32 && y_dtype != GTA_BF16) return fail(GTA_ERR_ARG, "aggregate_self: y_dtype must be F32 or BF16");
   return aggregate_impl(indptr, indices, n_rows, nnz, x_mode, x, ldx, F, x_dtype, w, ldw, heads, row_scale,
                         static_cast<float*>(y), ldy, 0, plan, plan_chunk, workspace, stream, x_self, ld_self, self_scale,
-                        y_dtype == GTA_BF16 ? 1 : 0);
+                        y_dtype == GTA_BF16 ? 1 : 0, nullptr, 0, /*f8_ok=*/true);
 }
 
 int64_t gta_aggregate_blocked_plan_bytes(int64_t n_rows, int64_t nnz, int64_t blocks, int64_t item_edges) {

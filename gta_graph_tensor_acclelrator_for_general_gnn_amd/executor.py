@@ -199,7 +199,7 @@ MAX_MATERIALIZE_BYTES = 96 << 30  # refuse to materialise a single edge tensor l
 class Executor:
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, dist=None,
                  softmax_shift=None, gather_dtype=None, multi_reduce=True, multi_reduce_blocked=False,
-                 mm_precision=None):
+                 mm_precision=None, fp8_rows=False):
         self.g = opgraph
         # dist (distributed.Comm): node tensors are this rank's row block; gathers are
         # reduce-scattered to it and dst-side scatters all-gather it (distributed.py)
@@ -288,6 +288,16 @@ class Executor:
                              f"not {gather_dtype}")
         self.gather_dtype = None if gather_dtype == torch.float32 else gather_dtype
         self.gather_casts = 0
+        #   fp8_rows: False (the default: every route and bit is unchanged), or True -- under gather_dtype
+        #   FP8, a source-gathered ADD aggregate that _spmm sends to the ROW-CHUNKED form (a table under
+        #   the blocked gate, or a width the blocked kernels do not take: GIN products' F = 100) gathers
+        #   the table -- fp32 or bf16 -- cast once by ops.to_fp8(lines=True): e4m3 rows on whole 128-B
+        #   lines (gta_aggregate with GTA_FP8, k_agg_rows_f8).  Widths <= 256, unweighted, one weight
+        #   per edge or heads over a multiple of 16 columns.  The self-term form is kept when x_self is
+        #   bf16 (it stays bf16); an fp32 x_self takes the accumulate path over the fp8 gather.  Opt-in:
+        #   the sums differ from the default's bits (within the bound on the rounded table).  Reducers
+        #   and the ORDER-C views see the option off.
+        self.fp8_rows = bool(fp8_rows)
         #   mm_precision: None or "f32" (the default: nothing changes), or "bf16x3" -- every MM whose
         #   operands are both fp32 after _mm_dtypes (_node_mm, the pushed-down MMs, _node_gemm, the edge /
         #   gather GEMM) runs as ops.update_mm(precision="bf16x3"): the bf16 MFMA on three-way splits,
@@ -1122,6 +1132,19 @@ class Executor:
             if xb is not xt:  # the callers count xt's rows per edge: take off what the narrower rows save
                 self.alg_bytes -= g.nnz * xt.shape[1] * (xt.element_size() - xb.element_size())
                 xt = xb
+        if not B and graph is None and self._fp8_rows_take(xt, mode, wt) and \
+                (acc is None or not (acc.stride(0) % 4 or acc.data_ptr() % 16)):  # (y rows 16-B aligned)
+            if self_term is not None:
+                xs, sc = self_term
+                # an fp32 x_self, or bf16 rows off the 16-B grid: the caller accumulates this gather into x * s
+                if xs.dtype != torch.bfloat16 or xs.stride(0) % 8 or xs.data_ptr() % 16 or \
+                        xs.shape[1] != xt.shape[1] or xs.shape[0] < g.n_rows:
+                    return None
+            xb = self._gather_cast(xt, rows=True)
+            self.alg_bytes -= g.nnz * xt.shape[1] * (xt.element_size() - xb.element_size())
+            if self_term is not None:
+                return ops.aggregate(g, xb, mode, wt, plan=self._plan(), self_term=self_term, out_dtype=out_dtype)
+            return ops.aggregate(g, xb, mode, wt, out=acc, accumulate=acc is not None, plan=self._plan())
         if self_term is not None:
             xs, sc = self_term
             if B or xs.dtype != xt.dtype or xs.shape[1] != xt.shape[1] or xs.shape[0] < g.n_rows:
@@ -1161,11 +1184,27 @@ class Executor:
             B = B if B >= 4 else 0
         return B if B and g.blocked_plan(B).sorted else 0
 
-    def _gather_cast(self, t, reduce=False):
+    def _fp8_rows_take(self, xt, mode, wt):
+        """Whether a row-chunked aggregate of xt runs over e4m3 rows (fp8_rows): what gta_aggregate
+        takes with GTA_FP8."""
+        if not (self.fp8_rows and self.gather_dtype == FP8 and mode == "src" and xt.shape[0] > 1
+                and xt.dtype in (torch.float32, torch.bfloat16) and xt.shape[1] <= 256 and xt.shape[1] % 4 == 0):
+            return False
+        F, H = xt.shape[1], (0 if wt is None else wt.shape[1])
+        return wt is None or (wt.dtype == torch.float32 and H != F and (H == 1 or (F % H == 0 and (F // H) % 16 == 0)))
+
+    def _gather_cast(self, t, reduce=False, rows=False):
         """The node table t as the blocked kernels gather it under gather_dtype: t itself (no option,
         or t already of that type), else its RNE rounding to bf16, or to e4m3 by ops.to_fp8 -- made
         once per table value and shared by its consumers (_memo: identity and version checked).
-        reduce: for a reducer route (_cast_dtype)."""
+        reduce: for a reducer route (_cast_dtype).  rows: for the row-chunked e4m3 aggregate
+        (fp8_rows): an fp32 or bf16 table as ops.to_fp8(lines=True) lays it out, in an entry of its own."""
+        if rows:
+            def cast_rows():
+                self._count(t.shape[0] * t.shape[1] * (t.element_size() + 1))
+                self.gather_casts += 1
+                return ops.to_fp8(t, lines=True)
+            return _memo(self._gather_cache, (id(t), "rows"), t, cast_rows)
         gd = self._cast_dtype(reduce)
         if gd is None or t.dtype != torch.float32:
             return t
@@ -1584,7 +1623,7 @@ def set_auto_graph(flag):
 
 
 def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=None, gather_dtype=None,
-                multi_reduce_blocked=False, mm_precision=None):
+                multi_reduce_blocked=False, mm_precision=None, fp8_rows=False):
     """-> a GraphedRun to replay for this call, or None (run eagerly)."""
     if ops.Tuning.attached(torch.cuda.current_stream(graph.device)):
         return None  # a knob set on this stream: every call reads it (gta.h), so no cached graph
@@ -1592,7 +1631,7 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_
     shifted = _shift_mode(softmax_shift)
     gdt = None if gather_dtype == torch.float32 else gather_dtype
     mmp = None if mm_precision == "f32" else mm_precision
-    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt, bool(multi_reduce_blocked), mmp), id(tensors), ops.knob_state())
+    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt, bool(multi_reduce_blocked), mmp, bool(fp8_rows)), id(tensors), ops.knob_state())
     ent = _AUTO_FAST.get(fkey)
     if ent is not None and not (ent.src is tensors and all(a is b for a, b in zip(ent.refs, refs)) and
                                 len(tensors) == len(ent.tensors) and
@@ -1627,7 +1666,7 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_
         try:
             ent.run = GraphedRun(opgraph, stream, graph, ent.tensors, semantics, plan_chunk, warmup=1,
                                  softmax_shift=shifted, gather_dtype=gdt, multi_reduce_blocked=multi_reduce_blocked,
-                                 mm_precision=mmp)
+                                 mm_precision=mmp, fp8_rows=fp8_rows)
         except Exception:  # something in this stream is not capturable: stay eager for this key
             ent.failed = True
             torch.cuda.synchronize(graph.device)
@@ -1656,8 +1695,9 @@ def _evict_pools(keep):
 
 
 def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, sync=True, trace=False,
-               softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None):
+               softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None, fp8_rows=False):
     """mm_precision: Executor.mm_precision for this call (None: every MM on its default route).
+    fp8_rows: Executor.fp8_rows for this call (False: today's routes).
     softmax_shift: Executor.softmax_shift for this call (None: the module's SOFTMAX_SHIFT).
     gather_dtype: Executor.gather_dtype for this call (None: tables are gathered as they are).
     multi_reduce_blocked: Executor.multi_reduce_blocked for this call (False: today's routes)."""
@@ -1666,7 +1706,7 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
         clear_auto_graphs()
     if AUTO_GRAPH and not trace and dev.type == "cuda" and graph.nnz <= AUTO_GRAPH_MAX_EDGES:
         gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift, gather_dtype,
-                         multi_reduce_blocked, mm_precision)
+                         multi_reduce_blocked, mm_precision, fp8_rows)
         if gr is not None:
             if sync:
                 torch.cuda.synchronize(dev)
@@ -1677,7 +1717,8 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
             ex = gr.executor
             return ExecResult(ex.values, outputs, time.perf_counter() - t0, ex.alg_bytes, ex.launches), ex
     ex = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
-                  gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked, mm_precision=mm_precision)
+                  gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked, mm_precision=mm_precision,
+                  fp8_rows=fp8_rows)
     ex.trace = trace
     sync = sync and dev.type == "cuda"
     if sync:
@@ -1865,7 +1906,7 @@ class GraphedRun:
     place (its version moved) is re-concatenated / re-transposed into them before the next replay."""
 
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, warmup=2,
-                 softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None):
+                 softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None, fp8_rows=False):
         if graph.device.type != "cuda":
             raise RuntimeError("GraphedRun captures device launches: the graph must be on a HIP device")
         self.tensors = tensors
@@ -1875,7 +1916,7 @@ class GraphedRun:
             for _ in range(max(1, warmup)):
                 Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
                          gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked,
-                         mm_precision=mm_precision).run()
+                         mm_precision=mm_precision, fp8_rows=fp8_rows).run()
         torch.cuda.current_stream(graph.device).wait_stream(side)
         torch.cuda.synchronize(graph.device)
         self.cuda_graph = torch.cuda.CUDAGraph()
@@ -1885,7 +1926,8 @@ class GraphedRun:
             with torch.cuda.graph(self.cuda_graph):
                 self.executor = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk,
                                          softmax_shift=softmax_shift, gather_dtype=gather_dtype,
-                                         multi_reduce_blocked=multi_reduce_blocked, mm_precision=mm_precision)
+                                         multi_reduce_blocked=multi_reduce_blocked, mm_precision=mm_precision,
+                                         fp8_rows=fp8_rows)
                 self.outputs = self.executor.run()
         finally:
             taken, ops._CAPTURED_WT[:] = list(ops._CAPTURED_WT), []

@@ -115,17 +115,20 @@ FP8 = torch.float8_e4m3fn  # OCP e4m3: what GTA_FP8 tables hold
 FP8_MAX = 448.0
 
 
-def to_fp8(t):
-    """t as an e4m3 (torch.float8_e4m3fn) node table for aggregate_blocked / gat_aggregate_blocked:
+def to_fp8(t, lines=False):
+    """t as an e4m3 (torch.float8_e4m3fn) node table for aggregate_blocked / gat_aggregate_blocked
+    and the row-chunked aggregate:
     clamped to +-448 (torch's cast does not saturate: 500 would become NaN), NaN kept, then rounded
     to nearest even by Tensor.to, on storage whose rows are 16-B aligned (pitch a multiple of 16
     bytes, padding zero).  No scaling: values are rounded as they are, so |x| > 448 saturates and
-    values below 2^-10 round to 0.  Pure torch, on any device; the CPU cast is the definition."""
+    values below 2^-10 round to 0.  Pure torch, on any device; the CPU cast is the definition.
+    lines: the pitch is line_pitch(F, 1) rounded up to 16 B -- whole 128-B lines where that lowers
+    the lines a gathered row touches (F = 100: 128 B, one line per row instead of 1.75)."""
     if t.dim() != 2:
         raise ValueError("to_fp8: a 2-D table")
     r = t.float().clamp(-FP8_MAX, FP8_MAX).to(FP8)  # clamp keeps NaN
     n, F = r.shape
-    P = -(-F // 16) * 16
+    P = -(-(line_pitch(F, 1) if lines else F) // 16) * 16
     if P == F and r.is_contiguous() and r.data_ptr() % 16 == 0:
         return r
     buf = torch.zeros(n, P, dtype=torch.uint8, device=r.device).view(FP8)
@@ -186,18 +189,24 @@ class AggregatePlan:
         return int(self.buf[8:16].view(torch.int64).item())
 
 
-def _gather_operand(graph, x, x_mode, who):
-    """(ldx, x_dt) of the rows a gather reads: float32, or bfloat16 gathered by index."""
-    if x.dtype == torch.bfloat16 and x_mode == "edge":
-        raise TypeError(f"{who}: bfloat16 rows are gathered by index (src / dst)")
-    ldx = _rows(x, "x", torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32)
+def _gather_operand(graph, x, x_mode, who, fp8=False):
+    """(ldx, x_dt) of the rows a gather reads: float32, or bfloat16 gathered by index; fp8 (the
+    aggregate alone): or e4m3 rows as to_fp8 lays them out, gathered by index (ldx in bytes)."""
+    if x.dtype in (torch.bfloat16, FP8) and x_mode == "edge":
+        raise TypeError(f"{who}: {x.dtype} rows are gathered by index (src / dst)")
+    if fp8 and x.dtype == FP8:
+        ldx = _fp8_rows(x, who)
+        if x.shape[1] > 256 or ldx < -(-x.shape[1] // 16) * 16:
+            raise ValueError(f"{who}: an fp8 x has at most 256 columns in whole 16-B pieces (ops.to_fp8 lays them out)")
+    else:
+        ldx = _rows(x, "x", torch.bfloat16 if x.dtype == torch.bfloat16 else torch.float32)
     if x_mode == "edge" and x.shape[0] < graph.nnz:
         raise ValueError("edge-mode x must have E rows")
     if x_mode == "src" and x.shape[0] < graph.n_cols:
         raise ValueError("src-mode x must have n_cols rows")
     if x_mode == "dst" and x.shape[0] < graph.n_rows:
         raise ValueError("dst-mode x must have n_rows rows")
-    return ldx, _lib.GTA_BF16 if x.dtype == torch.bfloat16 else _lib.GTA_F32
+    return ldx, _lib.GTA_FP8 if x.dtype == FP8 else (_lib.GTA_BF16 if x.dtype == torch.bfloat16 else _lib.GTA_F32)
 
 
 def _plan_args(graph, plan, F):
@@ -228,13 +237,17 @@ def aggregate(graph, x, x_mode="src", w=None, row_scale=None, out=None, accumula
 
     x_mode: "src" (x is [N_src, F], fused scatter C), "dst" (fused scatter R),
             "edge" (x is an edge tensor [E, F]).  x float32, or bfloat16 for "src" / "dst" with
-            head weights or none (rows widened exactly, fp32 sums).
+            head weights or none (rows widened exactly, fp32 sums), or e4m3 (torch.float8_e4m3fn as
+            to_fp8 lays it out, F <= 256) for "src" / "dst", unweighted, with one weight per edge or
+            with heads over a multiple of 16 columns: every code widened exactly, fp32 sums in an
+            order of its own (within the bound of the fp64 sum, not bitwise the fp32 call); its
+            self_term's x_self is bfloat16 on 16-B aligned rows.
     w: None, or [E, H] with H | F (H == F: full-width edge weights).
     plan: None (one wavefront per row), an AggregatePlan, or an int chunk (cached plan).
     """
     _need_gpu(x, w, row_scale, out, graph.indptr)
     F = x.shape[1]
-    ldx, x_dt = _gather_operand(graph, x, x_mode, "aggregate")
+    ldx, x_dt = _gather_operand(graph, x, x_mode, "aggregate", fp8=True)
     ldw, heads = 0, 0
     if w is not None:
         if w.dim() == 1:
@@ -251,8 +264,9 @@ def aggregate(graph, x, x_mode="src", w=None, row_scale=None, out=None, accumula
     if out is None:
         if out_dtype == torch.bfloat16:
             out = torch.empty(graph.n_rows, (F + 7) // 8 * 8, dtype=out_dtype, device=x.device)[:, :F]
-        else:
-            out = (torch.zeros if accumulate else torch.empty)(graph.n_rows, F, dtype=torch.float32, device=x.device)
+        else:  # (an fp8 x: 16-B aligned y rows)
+            P = (F + 3) // 4 * 4 if x.dtype == FP8 else F
+            out = (torch.zeros if accumulate else torch.empty)(graph.n_rows, P, dtype=torch.float32, device=x.device)[:, :F]
     ldy = _rows(out, "out", out_dtype)
     if out.shape[0] < graph.n_rows or out.shape[1] != F:
         raise ValueError("out must be [N, F]")
@@ -261,8 +275,9 @@ def aggregate(graph, x, x_mode="src", w=None, row_scale=None, out=None, accumula
     pbuf, ws, chunk = _plan_args(graph, plan, F)
     if self_term is not None:
         xs, sc = self_term
-        if accumulate or xs.dtype != x.dtype or xs.shape[0] < graph.n_rows or xs.shape[1] != F:
-            raise ValueError("aggregate self_term: x_self [N, F] of x's dtype, no accumulate")
+        xs_dt = torch.bfloat16 if x.dtype == FP8 else x.dtype
+        if accumulate or xs.dtype != xs_dt or xs.shape[0] < graph.n_rows or xs.shape[1] != F:
+            raise ValueError("aggregate self_term: x_self [N, F] of x's dtype (bfloat16 beside an fp8 x), no accumulate")
         if sc.dtype != torch.float32 or sc.numel() != 1:
             raise ValueError("aggregate self_term: s must be a one-element float32 tensor")
         _need_gpu(xs, sc)

@@ -63,14 +63,17 @@ extern "C" {
                               products on the bf16 MFMA; no new symbol, no signature changes);
                               15 (additive): online softmax in the fused GAT aggregate
                               (gta_gat_aggregate_blocked_online and its workspace size; no existing
-                              signature changes) */
+                              signature changes);
+                              15 (additive): GTA_FP8 rows in gta_aggregate / gta_aggregate_self (the
+                              row-chunked form; no new symbol, no signature changes) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
 
 /* dtypes; GTA_F32_BF16 (update_mm only): fp32 x rounded to bf16 (RNE) as it is
  * staged into LDS, bf16 W -- no separate cast pass over x.
- * GTA_FP8 (gta_aggregate_blocked_x / gta_gat_aggregate_blocked_x only): OCP e4m3fn, one byte per
+ * GTA_FP8 (gta_aggregate_blocked_x / gta_gat_aggregate_blocked_x, and gta_aggregate /
+ * gta_aggregate_self: "GTA_FP8 rows" there; every other entry point refuses it): OCP e4m3fn, one byte per
  * element -- sign s, exponent e (4 bits), mantissa m (3 bits): +-m 2^-9 for e = 0 (denormals),
  * +-(1 + m/8) 2^(e-7) otherwise, largest value 448; no infinities, codes 0x7f / 0xff are NaN,
  * 0x80 is -0.
@@ -185,6 +188,19 @@ int gta_scatter(int dir, const int64_t* indptr, const int32_t* indices, int64_t 
  * x_dtype: GTA_F32, or GTA_BF16 for x_mode SRC / DST with w NULL or head weights
  *          (rows widened exactly to fp32, sums in fp32: the 2-byte gathers of BASELINE.md's
  *          GIN byte model).
+ *          GTA_FP8 rows (ABI 15 additive; also in gta_aggregate_self): x holds e4m3 rows, ldx in
+ *          BYTES; x 16-B aligned, ldx % 16 == 0 and ldx >= 16 ceil(F / 16) (a row's last 16-B piece
+ *          is read whole, its bytes past column F ignored); x_mode SRC or DST; 1 <= F <= 256; w
+ *          NULL, heads == 1, or heads with (F / heads) % 16 == 0; y rows 16-B aligned (y 16-B
+ *          aligned, ldy % 4 == 0; a bf16 y: ldy % 8 == 0).  Anything else -- x_mode EDGE, heads == F,
+ *          another head width, F > 256, a misaligned x or y -- is GTA_ERR_UNSUPPORTED, decided
+ *          before any device work (y untouched).  Every code widens exactly (denormals, -0 and the
+ *          two NaN codes included); sums are fp32: 64 / LPR edge slots (LPR the smallest power of two
+ *          >= ceil(F / 16)), slot s summing edges s, s + 64 / LPR, ... of the item in order, then
+ *          a fixed fold of the slots.  Deterministic (two calls are bitwise equal) and within the
+ *          fp32 summation bound of the exact sum of the widened table, but NOT bitwise the GTA_F32
+ *          call on the widened table (the slot count differs).  One 128-B line per gathered row
+ *          for F <= 128 at a 128-B pitch.
  * workspace: >= gta_aggregate_workspace_bytes(...) when plan != NULL.
  * Reference: hardware_info.yaml Inst_fused [applyedge,gather] [MUL,ADD]
  * ("FinalVersion For Paper/hardware_info.yaml":35-38), inst_fusion_x2
@@ -289,7 +305,10 @@ int gta_reduce_multi(int which, const int64_t* indptr, const int32_t* indices, i
  * (genGraphOP.py:99-103): agg + (1 + eps) x with no [N, F] intermediate.
  * y_dtype (ABI 10): GTA_F32, or GTA_BF16 -- y holds the RNE bf16 rounding of the fp32 value (ldy in
  * bf16 elements), for a consumer that rounds its input to bf16 anyway (gta_update_mlp: GIN's MLP
- * after ops 3-4), so half the bytes are written and read and the value it sees is unchanged. */
+ * after ops 3-4), so half the bytes are written and read and the value it sees is unchanged.
+ * x_dtype GTA_FP8 (gta_aggregate's "GTA_FP8 rows"): the one exception to "x_self has x's dtype" --
+ * x_self holds BF16 rows (ld_self in bf16 elements, x_self 16-B aligned, ld_self % 8 == 0): the
+ * node's own feature stays at the table's storage precision, only the gathered neighbours are e4m3. */
 int gta_aggregate_self(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, int x_mode,
                        const void* x, int64_t ldx, int64_t F, int x_dtype, const float* w, int64_t ldw, int64_t heads,
                        const float* row_scale, const void* x_self, int64_t ld_self, const float* self_scale, void* y,
