@@ -85,6 +85,9 @@ SIGNATURES = {
     "gta_update_mm_t_split_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "gta_update_mm_t_split": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i64, _vp,
                                      _i64, _vp]),
+    "gta_aggregate_edge_mm_workspace_bytes": (_i64, [_i64, _i64]),
+    "gta_aggregate_edge_mm": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64,
+                                     _i32, _vp, _i64, _vp, _vp]),
     "gta_tile_nnz": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "gta_synth_alpha": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _i64, _vp, _vp]),
     "gta_row_ids": (_i32, [_vp, _i64, _i64, _vp, _vp]),

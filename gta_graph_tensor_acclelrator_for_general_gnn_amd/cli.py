@@ -80,6 +80,9 @@ def parser():
     p.add_argument("--fp8-rows", action="store_true",
                    help="with --gather-dtype fp8: the row-chunked ADD aggregates (narrow rows, e.g. F = 100) gather "
                         "e4m3 rows on whole 128-B lines too (off: they gather the table as it is)")
+    p.add_argument("--edge-mm-gather", action="store_true",
+                   help="PNA: the edge MM, its ADDs, the SF and the gather in one launch, no [E, fout] product in "
+                        "memory (off: the GEMM, then the expression gather; the sums' last bits differ)")
     p.add_argument("--mm-precision", choices=["f32", "bf16x3"], default="f32",
                    help="fp32 x fp32 MMs: f32 = the fp32 MFMA kernels; bf16x3 = the bf16 MFMA on three-way bf16 splits of "
                         "both operands (fp32-level accuracy, other last bits)")
@@ -118,6 +121,8 @@ def run(args, device, log=print):
             kw["mm_precision"] = args.mm_precision
         if getattr(args, "fp8_rows", False):
             kw["fp8_rows"] = True
+        if getattr(args, "edge_mm_gather", False):
+            kw["edge_mm_gather"] = True
         lay = None
         for k, (op_array, tile_size_list) in enumerate(c[:2] for c in cands):
             try:

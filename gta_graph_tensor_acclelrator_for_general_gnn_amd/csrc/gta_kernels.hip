@@ -4578,9 +4578,10 @@ constexpr int ring_blocks(int NT, int D, int FR) {
   return (160 / (D * (4 * FR + NT))) > 4 ? 4 : (160 / (D * (4 * FR + NT)));
 }
 
-// The persistent ring schedule, as k_mm_ring_bf runs it (k_mm_ring below keeps the same schedule
-// written out: with these shared pieces its 64-row forms measured 5 - 11 % slower, DESIGN.md 3.8;
-// until that cause is found RingSched and ring_run have this one caller).  A block's row groups
+// The persistent ring schedule, as k_mm_ring_bf and k_emm_gather run it (k_mm_ring below keeps the
+// same schedule written out: with these shared pieces its 64-row forms measured 5 - 11 % slower,
+// DESIGN.md 3.8, and that cause is still open; k_emm_gather takes the shared pieces knowingly, see
+// its header).  A block's row groups
 // are grp0, grp0 + gstep, ...; the ring runs on across them (stage t = (group j, step s) of S per
 // group), so the next group's first stages land while this group finishes and no block pays a
 // prologue after the first.  (j, s, slot) is the next stage to DMA as (group, stage in group, ring
@@ -4927,6 +4928,230 @@ k_mm_ring(const float* __restrict__ x, int64_t ldx, const int32_t* __restrict__ 
   // the counted waits above assume only ring DMA is outstanding; stores may retire out of order
   // with the loads, so drain them here (the next group's first stages have had a step to land)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+}
+
+// ---- fused edge GEMM + gather (gta_aggregate_edge_mm, gta.h): PNA's applyedge MM, its two ADDs, the
+// SF and the gather R in one pass -- `vTCAD/GraphOP/genGraphOP.py` PNA ops 2, 5-8; the reference's fused
+// [applyedge, gather] (MM, ADD) instruction.  y[i] = sum_{e in row i} sf(ef[e] . W + p[src(e)] + q[i]).
+// A row group of the ring GEMM is 64 consecutive CSR edges with all N columns in one workgroup
+// (N = 16 NT, one column block), so the product tile never leaves the CU: the waves put their MFMA
+// fragments into an LDS tile and the block walks it in two segments of kEmmSeg edges, one thread per
+// (segment, column), summing each destination row's edges in edge order.  A row that lies inside
+// its segment is stored to y; a row cut by a segment boundary leaves one partial per segment in
+// the slab ([segment][0]: the row began before the segment, [1]: it goes on past it) and
+// k_emm_finish adds a row's partials in segment order.  No atomics: the order is fixed by nnz.
+// The mainloop runs on RingSched / ring_run, not on a third written-out copy of the schedule: a
+// deliberate choice of one loop to keep right over the 5 - 11 % the shared pieces cost k_mm_ring's
+// 64-row forms; the route is opt-in and measured slower than the unfused pair.
+// The tile has no barrier of its own between group j's walk and group j + 1's tile write: the
+// S >= 1 stage barriers of group j + 1 inside ring_run stand between them, every wave reaching the
+// first only after its walk.  That needs a ring stage per group, K >= kEmmMinK (a K < 16 product
+// has no stages, T = 0: "the tail does it all"), which gta_aggregate_edge_mm refuses below.
+constexpr int kEmmSeg = 32;   // edges per walked segment: a 64-edge group is two
+constexpr int kEmmMinK = 32;  // smallest K taken: at least two ring stages between two tile writes
+
+struct EmmArgs {
+  const int64_t* indptr;
+  const int32_t* indices;
+  int64_t n_rows, nnz;
+  const float* p;  // [n_cols][ldp] read at indices[e], or NULL
+  int64_t ldp;
+  const float* q;  // [n_rows][ldq] read at the edge's row, or NULL
+  int64_t ldq;
+  float* y;
+  int64_t ldy;
+  float* slab;  // [ceil(nnz / kEmmSeg)][2][N]
+};
+
+// One segment, one column: edges [sg * kEmmSeg, +kEmmSeg) of the CSR in order.  tile: the segment's
+// first product row at this thread's column (row pitch `pitch` floats).  Everything but col is
+// wave-uniform.  Per edge z = m + (p + q) (a NULL operand leaves its add out), t = SFK(z), each an
+// fp32 value as the unfused ops store it (no contraction); p rows are fetched 8 edges ahead of the
+// sums so their latencies overlap.
+template <int SFK, int N>
+__device__ __forceinline__ void emm_walk(const EmmArgs& a, const float* tile, int pitch, int64_t sg, int col) {
+#pragma clang fp contract(off)
+  const int64_t e0 = sg * kEmmSeg;
+  if (e0 >= a.nnz) return;
+  const int64_t e1 = min<int64_t>(e0 + kEmmSeg, a.nnz);
+  int64_t lo = 0, hi = a.n_rows;  // indptr[lo] <= e0 < indptr[hi]: the row that holds edge e0
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (a.indptr[mid] <= e0) lo = mid; else hi = mid;
+  }
+  int64_t row = lo, rbeg = a.indptr[row], rend = a.indptr[row + 1];
+  const bool hp = a.p != nullptr, hq = a.q != nullptr;
+  float qv = hq ? a.q[row * a.ldq + col] : 0.f;
+  float acc = 0.f;
+  auto flush = [&]() __attribute__((always_inline)) {  // the sum of row's edges inside this segment
+    if (rbeg >= e0 && rend <= e1) a.y[row * a.ldy + col] = acc;
+    else a.slab[(sg * 2 + (rbeg < e0 ? 0 : 1)) * N + col] = acc;
+  };
+#pragma unroll 1
+  for (int b = 0; b < kEmmSeg && e0 + b < e1; b += 8) {
+    float pv[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t e = min<int64_t>(e0 + b + k, e1 - 1);
+      pv[k] = hp ? a.p[static_cast<int64_t>(a.indices[e]) * a.ldp + col] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int64_t e = e0 + b + k;
+      if (e < e1) {
+        if (e == rend) {  // the row is done: the next row with an edge (empty rows in between have none)
+          flush();
+          do {
+            ++row;
+            rend = a.indptr[row + 1];
+          } while (rend <= e && row + 1 < a.n_rows);
+          rbeg = e;
+          qv = hq ? a.q[row * a.ldq + col] : 0.f;
+          acc = 0.f;
+        }
+        const float m = tile[(b + k) * pitch];
+        const float z = hp ? (hq ? m + (pv[k] + qv) : m + pv[k]) : (hq ? m + qv : m);
+        acc += sf_apply(SFK, z);
+      }
+    }
+  }
+  flush();
+}
+
+template <int NT>
+__global__ void __launch_bounds__(kBlock, 2)
+k_emm_gather(const float* __restrict__ x, int64_t ldx, int K, const float* __restrict__ wt, int64_t ldwt, int sf,
+             EmmArgs a) {
+  static_assert(NT == 4 || NT == 8, "B fragments split evenly over the 4 waves; N = 16 NT is the one column block");
+  constexpr int D = 3, FR = 1, KS = 16, N = 16 * NT, GR = 64;
+  static_assert(kEmmMinK >= KS, "a ring stage (and its block barrier) between two groups' tile writes");
+  // k_mm_ring's stage image: A [wave] then B [c], 1 KiB fragments (16 rows x 16 k), its DMA lane
+  // map and XOR swizzle, its k order and K-tail rules (ring tail for K % 4 == 0, register tail else)
+  constexpr int A_BYTES = 4 * FR * 1024, STAGE = A_BYTES + NT * 1024;
+  constexpr int PER_STAGE = FR + NT / 4;
+  // the product tile [64 edges][N], pitch N + 4 floats: the four lane groups of an MFMA fragment
+  // (rows 4g + r) land 4 banks apart, so a fragment's 64 dword stores hit 64 banks.  LDS at N = 128:
+  // ring 36 KiB + tile 33 KiB = 69 KiB, two blocks per CU in 160 KB (N = 64: 24 + 17 KiB)
+  constexpr int PITCH = N + 4;
+  __shared__ __attribute__((aligned(16))) char lds[D * STAGE];
+  __shared__ __attribute__((aligned(16))) float tile[GR * PITCH];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wv = wave_id_uniform();
+  const int g = lane >> 4, r16 = lane & 15;
+  const int64_t M = a.nnz;
+  const bool ring_tail = (K % KS) != 0 && (K % 4) == 0;
+  const int S = ring_tail ? (K + KS - 1) / KS : K / KS;
+  RingSched<D> rs(1, (M + GR - 1) / GR, S);
+  const int rr = lane >> 2;
+  const int cdma = (lane & 3) ^ ((rr >> 2) & 2);  // logical 16-B k piece this lane DMAs
+  const uint32_t rdoff = static_cast<uint32_t>(r16 * 64 + ((g ^ ((r16 >> 2) & 2)) * 16));
+  const bool dead = ring_tail && (S - 1) * KS + 4 * cdma >= K;  // this lane's DMA piece of the last stage
+  const bool dead_rd = ring_tail && (S - 1) * KS + 4 * g >= K;  // the piece this lane reads
+  const float* bsrc[NT / 4];
+#pragma unroll
+  for (int t = 0; t < NT / 4; ++t) bsrc[t] = wt + static_cast<int64_t>(16 * (wv * (NT / 4) + t) + rr) * ldwt + 4 * cdma;
+  auto a_row = [&](int64_t j, int sub) __attribute__((always_inline)) -> const float* {  // edges past nnz: the last
+    return x + min<int64_t>(rs.first_row(j, GR) + wv * 16 + sub, M - 1) * ldx;
+  };
+  const float* asrc = nullptr;
+  int64_t asrc_j = -1;  // the group asrc holds the row of
+  auto issue = [&]() __attribute__((always_inline)) {  // the DMA of stage rs.(j, s) into rs.slot
+    if (rs.j != asrc_j) {
+      asrc_j = rs.j;
+      asrc = a_row(rs.j, rr) + 4 * cdma;
+    }
+    char* base = lds + rs.slot * STAGE;
+    const int ko = (dead && rs.s == S - 1) ? -4 * cdma : rs.s * KS;  // a piece past K reads its row's start
+    rs.advance();
+    __builtin_amdgcn_global_load_lds(const_cast<float*>(asrc + ko), GTA_TO_LDS(base + wv * 1024), 16, 0, 0);
+#pragma unroll
+    for (int t = 0; t < NT / 4; ++t)
+      __builtin_amdgcn_global_load_lds(const_cast<float*>(bsrc[t] + ko),
+                                       GTA_TO_LDS(base + A_BYTES + (wv * (NT / 4) + t) * 1024), 16, 0, 0);
+  };
+  f32x4 acc[FR][NT];
+  auto stage = [&](int slot, int s) __attribute__((always_inline)) {
+    const uint32_t sa = GTA_LDS_ADDR(lds + slot * STAGE + wv * 1024) + rdoff;
+    const uint32_t sb = GTA_LDS_ADDR(lds + slot * STAGE + A_BYTES) + rdoff;
+    f32x4 a4[FR], b4[NT];
+    ds_read16_kib(a4[0], sa, 0);
+#pragma unroll
+    for (int c = 0; c < NT; ++c) ds_read16_kib(b4[c], sb, c);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    asm volatile("" : "+v"(a4[0]));
+#pragma unroll
+    for (int c = 0; c < NT; ++c) asm volatile("" : "+v"(b4[c]));
+    if (dead_rd && s == S - 1) {  // pieces past K: zeros
+      a4[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < NT; ++c) b4[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    mma_f32_step(acc, a4, b4);
+  };
+  auto tail = [&](int64_t j) __attribute__((always_inline)) {  // k in [16 S, K) from registers, zeros past K
+    if (ring_tail) return;
+    for (int kt = S * KS; kt < K; kt += KS) {
+      const int k0 = kt + 4 * g;
+      auto ld4 = [&](const float* p) __attribute__((always_inline)) {  // p = row + k0
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (k0 + q < K) v[q] = p[q];
+        return v;
+      };
+      f32x4 a4[FR], b4[NT];
+      a4[0] = ld4(a_row(j, r16) + k0);
+#pragma unroll
+      for (int c = 0; c < NT; ++c) b4[c] = ld4(wt + static_cast<int64_t>(16 * c + r16) * ldwt + k0);
+      mma_f32_step(acc, a4, b4);
+    }
+  };
+  // the walk's thread map: wave wv walks segment sl, columns col0 .. col0 + 63 (N = 64: waves 0 and 1)
+  const int sl = wv * kWave / N, col = (wv * kWave) % N + lane;
+  auto epilogue = [&](int64_t j) __attribute__((always_inline)) {
+    // (every wave is past the previous group's walk: a stage barrier lies in between)
+#pragma unroll
+    for (int c = 0; c < NT; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tile[(wv * 16 + 4 * g + r) * PITCH + 16 * c + r16] = acc[0][c][r];
+    __syncthreads();
+    if (sl < GR / kEmmSeg) {
+      const int64_t sg = (rs.grp0 + j * rs.gstep) * (GR / kEmmSeg) + sl;
+      const float* trow = tile + sl * kEmmSeg * PITCH + col;
+      switch (sf) {
+#define GTA_EMM_SF(K_) case K_: emm_walk<K_, N>(a, trow, PITCH, sg, col); break;
+        GTA_EMM_SF(GTA_SF_RELU) GTA_EMM_SF(GTA_SF_EXP_LEAKY_RELU) GTA_EMM_SF(GTA_SF_ELU) GTA_EMM_SF(GTA_SF_EXP)
+        GTA_EMM_SF(GTA_SF_LEAKY_RELU) GTA_EMM_SF(GTA_SF_SIGMOID) GTA_EMM_SF(GTA_SF_TANH) GTA_EMM_SF(GTA_SF_RECIP)
+#undef GTA_EMM_SF
+        default: emm_walk<GTA_SF_NONE, N>(a, trow, PITCH, sg, col); break;
+      }
+    }
+    // (ring_run drains the walk's loads and stores before the ring's counted waits resume)
+  };
+  ring_run<PER_STAGE>(rs, acc, issue, stage, tail, epilogue);
+}
+
+// The rows k_emm_gather did not finish, one wave per row: a row without edges is 0 (not sf(0)); a
+// row whose edges span segments s0 < s1 is slab[s0][1] + slab[s0 + 1][0] + ... + slab[s1][0], added
+// in that order; a row inside one segment was stored by the walk and is left alone.
+__global__ void __launch_bounds__(kBlock)
+k_emm_finish(const int64_t* __restrict__ indptr, int64_t n_rows, int N, const float* __restrict__ slab,
+             float* __restrict__ y, int64_t ldy) {
+#pragma clang fp contract(off)
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave_id_uniform();
+  if (row >= n_rows) return;
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t rb = indptr[row], re = indptr[row + 1];
+  const int64_t s0 = rb / kEmmSeg, s1 = re > rb ? (re - 1) / kEmmSeg : s0;
+  if (re > rb && s0 == s1) return;
+  for (int c = lane; c < N; c += kWave) {
+    float acc = 0.f;
+    if (re > rb) {
+      acc = slab[(s0 * 2 + 1) * N + c];
+      for (int64_t s = s0 + 1; s <= s1; ++s) acc += slab[(s * 2) * N + c];
+    }
+    y[row * ldy + c] = acc;
   }
 }
 
@@ -7994,6 +8219,44 @@ int gta_update_mm_t_split(const void* x, int64_t ldx, const int32_t* row_idx, in
                       s>>>(ws, static_cast<int>(nsl), M, static_cast<int>(N), sf, out, ldo);
   }
   GTA_LAUNCHED("k_mm_slices_sum");
+  return GTA_OK;
+}
+
+int64_t gta_aggregate_edge_mm_workspace_bytes(int64_t nnz, int64_t N) {
+  if (nnz < 0 || N <= 0) return fail(GTA_ERR_ARG, "aggregate_edge_mm_workspace_bytes: bad sizes");
+  return (nnz + kEmmSeg - 1) / kEmmSeg * 2 * N * static_cast<int64_t>(sizeof(float));
+}
+
+int gta_aggregate_edge_mm(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz, const float* ef,
+                          int64_t ldef, int64_t K, const void* wt, int64_t ldwt, int64_t N, int dtype, const float* p,
+                          int64_t ldp, const float* q, int64_t ldq, int sf, float* y, int64_t ldy, void* workspace,
+                          void* stream) {
+  const auto bad = [](int code, const char* what) { return fail(code, std::string("aggregate_edge_mm: ") + what); };
+  if (n_rows < 0 || nnz < 0 || K <= 0 || N <= 0) return bad(GTA_ERR_ARG, "bad sizes");
+  if (dtype < GTA_F32 || dtype > GTA_F32_BF16X3) return bad(GTA_ERR_ARG, "bad dtype");
+  if (sf < GTA_SF_NONE || sf > GTA_SF_RECIP) return bad(GTA_ERR_ARG, "bad sf");
+  if (!indptr || !y || (nnz > 0 && (!indices || !ef || !wt || !workspace))) return bad(GTA_ERR_ARG, "NULL argument");
+  if (ldef < K || ldwt < K || ldy < N || (p && ldp < N) || (q && ldq < N)) return bad(GTA_ERR_ARG, "a row stride below its width");
+  if (dtype != GTA_F32) return bad(GTA_ERR_UNSUPPORTED, "GTA_F32 only");
+  // (K >= kEmmMinK is also what keeps k_emm_gather's LDS tile race-free: see its header)
+  if ((N != 64 && N != 128) || K < kEmmMinK || K > INT32_MAX) return bad(GTA_ERR_UNSUPPORTED, "N must be 64 or 128 and K >= 32");
+  const auto rows16 = [](const void* t, int64_t ld) { return !t || (aligned(t, 16) && ld % 4 == 0); };
+  if (!rows16(wt, ldwt) || !rows16(y, ldy) || !rows16(p, ldp) || !rows16(q, ldq) || !aligned(ef, 4))
+    return bad(GTA_ERR_UNSUPPORTED, "W^T, y, p and q rows must be 16-B aligned");
+  if (n_rows == 0) return GTA_OK;
+  if ((n_rows + kWavesPerBlock - 1) / kWavesPerBlock > INT32_MAX) return bad(GTA_ERR_UNSUPPORTED, "too many rows");
+  float* slab = static_cast<float*>(workspace);
+  if (nnz > 0) {
+    const EmmArgs a{indptr, indices, n_rows, nnz, p, ldp, q, ldq, y, ldy, slab};
+    const dim3 gr(static_cast<unsigned>(persistent_blocks((nnz + 63) / 64, 1, 2)));
+    const float* w = static_cast<const float*>(wt);
+    if (N == 128) k_emm_gather<8><<<gr, dim3(kBlock), 0, S(stream)>>>(ef, ldef, static_cast<int>(K), w, ldwt, sf, a);
+    else k_emm_gather<4><<<gr, dim3(kBlock), 0, S(stream)>>>(ef, ldef, static_cast<int>(K), w, ldwt, sf, a);
+    GTA_LAUNCHED("k_emm_gather");
+  }
+  k_emm_finish<<<dim3(static_cast<unsigned>((n_rows + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, S(stream)>>>(
+      indptr, n_rows, static_cast<int>(N), slab, y, ldy);
+  GTA_LAUNCHED("k_emm_finish");
   return GTA_OK;
 }
 

@@ -199,7 +199,8 @@ MAX_MATERIALIZE_BYTES = 96 << 30  # refuse to materialise a single edge tensor l
 class Executor:
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, dist=None,
                  softmax_shift=None, gather_dtype=None, multi_reduce=True, multi_reduce_blocked=False,
-                 mm_precision=None, fp8_rows=False):
+                 mm_precision=None, fp8_rows=False,
+                 edge_mm_gather=False):
         self.g = opgraph
         # dist (distributed.Comm): node tensors are this rank's row block; gathers are
         # reduce-scattered to it and dst-side scatters all-gather it (distributed.py)
@@ -338,6 +339,16 @@ class Executor:
         self.edge_expr = EDGE_EXPR
         self.expr = rewrites.edge_expr(opgraph, cons, self.sem, self.softmax, self.attn, self.pushdown, self.gacc)
         self.expr_nodes = {i for e in self.expr.values() for i in e["nodes"]}
+        #   edge_mm_gather: False (the default: every route and bit is unchanged), or True -- an edge_expr
+        #   tree of ADDs whose one leaf is an applyedge MM of an edge tensor read by nothing else (PNA op
+        #   2) and whose other leaves are virtual scatters runs as ONE ops.aggregate_edge_mm: the edge
+        #   GEMM, the ADDs, the SF and the sum, with no [E, fout] product in HBM (the reference's fused
+        #   [applyedge, gather] (MM, ADD)).  Within the fp32 bound of the unfused pair, not its bits.  A
+        #   shape the kernel refuses (fout not 64 / 128, bf16 weights, mm_precision bf16x3) keeps
+        #   today's path; the MM's own value stays available, computed unfused if read.
+        self.edge_mm_gather = bool(edge_mm_gather)
+        self.emm = rewrites.edge_mm_gather(opgraph, cons, self.expr) if self.edge_mm_gather and dist is None else {}
+        self.emm_mm = {mm for _, mm in self.emm.values()}
 
     # ---------------------------------------------------------------- inputs
     def _ext(self, op, slot):
@@ -447,6 +458,10 @@ class Executor:
         e = self.expr[G.idx]
         if not all(self._pending(i) for i in e["nodes"]):
             return None
+        if G.idx in self.emm:
+            y = self._eval_edge_mm_gather(e, *self.emm[G.idx])
+            if y is not None:
+                return y
         operands, gathered = [], 0
         for ref in e["leaves"]:
             if ref[0] == "pmm":
@@ -481,6 +496,30 @@ class Executor:
         n, E = self.graph.n_rows, self.graph.nnz
         self._count(self._gather_bytes(E, n, F, 4 * gathered))  # fp32 rows of every gathered operand
         return NodeT(self.dist.reduce_rows(y) if self.dist is not None else y)
+
+    def _eval_edge_mm_gather(self, e, k, mm):
+        """The tree of plan e, whose leaf k is the still-unformed edge MM op mm, from one
+        ops.aggregate_edge_mm launch (edge_mm_gather); None keeps _eval_edge_expr's own path."""
+        mop, W = self.g.ops[mm], self.tensors[f"w:{mm}"]
+        if not self._pending(mm) or W.dtype != torch.float32 or self.mm_precision == "bf16x3":
+            return None
+        ef = self._source(mop, 0)  # (a model / external input: wrapped, not computed)
+        if not isinstance(ef, EdgeT) or ef.t.dtype != torch.float32 or ef.t.shape[1] != W.shape[0]:
+            return None
+        pq = {}
+        for l, ref in enumerate(e["leaves"]):
+            if l != k:  # (the leaves the expression gather would evaluate next anyway, memoised)
+                v = self._source(self.g.ops[ref[0]], ref[1])
+                if not isinstance(v, Scat) or v.mode in pq or v.t.shape[1] != W.shape[1]:
+                    return None
+                pq[v.mode] = self._fp32(v.t)
+        y = ops.aggregate_edge_mm(self.graph, ef.t, W, pq.get("src"), pq.get("dst"), e["sfs"][e["shape"] - 1])
+        if y is None:
+            return None
+        n, E, (K, N) = self.graph.n_rows, self.graph.nnz, W.shape
+        # ef and W once, a p row per edge, q and y once
+        self._count(4 * (E * K + K * N + E * N * ("src" in pq) + n * N * ("dst" in pq) + n * N))
+        return NodeT(y)
 
     def _self_term(self, top):
         """(x, s) when node op T = applynode MUL(x, s) of a node tensor x by a one-element scalar s
@@ -1260,6 +1299,9 @@ class Executor:
         if expr and self.edge_expr and op.idx in self.expr_nodes:
             # a node of a fused expression tree: its gather runs it; computed unfused only if read
             return Lazy(lambda: _forced(self._eval(op, block, expr=False)))
+        if expr and self.edge_expr and op.idx in self.emm_mm:
+            # the MM leaf of a tree that aggregate_edge_mm may run whole: the unfused GEMM only if read
+            return Lazy(lambda: _forced(self._eval(op, block, expr=False)))
         fused_into = {p: c for p, c, _ in block.fused}
         if op.type == "scatter":
             src = self.g.inputs[op.idx][0]
@@ -1623,7 +1665,7 @@ def set_auto_graph(flag):
 
 
 def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=None, gather_dtype=None,
-                multi_reduce_blocked=False, mm_precision=None, fp8_rows=False):
+                multi_reduce_blocked=False, mm_precision=None, fp8_rows=False, edge_mm_gather=False):
     """-> a GraphedRun to replay for this call, or None (run eagerly)."""
     if ops.Tuning.attached(torch.cuda.current_stream(graph.device)):
         return None  # a knob set on this stream: every call reads it (gta.h), so no cached graph
@@ -1631,7 +1673,7 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_
     shifted = _shift_mode(softmax_shift)
     gdt = None if gather_dtype == torch.float32 else gather_dtype
     mmp = None if mm_precision == "f32" else mm_precision
-    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt, bool(multi_reduce_blocked), mmp, bool(fp8_rows)), id(tensors), ops.knob_state())
+    fkey = (id(opgraph), id(stream), id(graph), id(semantics), (plan_chunk, shifted, gdt, bool(multi_reduce_blocked), mmp, bool(fp8_rows), bool(edge_mm_gather)), id(tensors), ops.knob_state())
     ent = _AUTO_FAST.get(fkey)
     if ent is not None and not (ent.src is tensors and all(a is b for a, b in zip(ent.refs, refs)) and
                                 len(tensors) == len(ent.tensors) and
@@ -1666,7 +1708,7 @@ def _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_
         try:
             ent.run = GraphedRun(opgraph, stream, graph, ent.tensors, semantics, plan_chunk, warmup=1,
                                  softmax_shift=shifted, gather_dtype=gdt, multi_reduce_blocked=multi_reduce_blocked,
-                                 mm_precision=mmp, fp8_rows=fp8_rows)
+                                 mm_precision=mmp, fp8_rows=fp8_rows, edge_mm_gather=edge_mm_gather)
         except Exception:  # something in this stream is not capturable: stay eager for this key
             ent.failed = True
             torch.cuda.synchronize(graph.device)
@@ -1695,9 +1737,11 @@ def _evict_pools(keep):
 
 
 def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, sync=True, trace=False,
-               softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None, fp8_rows=False):
+               softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None, fp8_rows=False,
+               edge_mm_gather=False):
     """mm_precision: Executor.mm_precision for this call (None: every MM on its default route).
     fp8_rows: Executor.fp8_rows for this call (False: today's routes).
+    edge_mm_gather: Executor.edge_mm_gather for this call (False: today's routes).
     softmax_shift: Executor.softmax_shift for this call (None: the module's SOFTMAX_SHIFT).
     gather_dtype: Executor.gather_dtype for this call (None: tables are gathered as they are).
     multi_reduce_blocked: Executor.multi_reduce_blocked for this call (False: today's routes)."""
@@ -1706,7 +1750,7 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
         clear_auto_graphs()
     if AUTO_GRAPH and not trace and dev.type == "cuda" and graph.nnz <= AUTO_GRAPH_MAX_EDGES:
         gr = _auto_graph(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift, gather_dtype,
-                         multi_reduce_blocked, mm_precision, fp8_rows)
+                         multi_reduce_blocked, mm_precision, fp8_rows, edge_mm_gather)
         if gr is not None:
             if sync:
                 torch.cuda.synchronize(dev)
@@ -1718,7 +1762,7 @@ def run_stream(opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, 
             return ExecResult(ex.values, outputs, time.perf_counter() - t0, ex.alg_bytes, ex.launches), ex
     ex = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
                   gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked, mm_precision=mm_precision,
-                  fp8_rows=fp8_rows)
+                  fp8_rows=fp8_rows, edge_mm_gather=edge_mm_gather)
     ex.trace = trace
     sync = sync and dev.type == "cuda"
     if sync:
@@ -1906,7 +1950,8 @@ class GraphedRun:
     place (its version moved) is re-concatenated / re-transposed into them before the next replay."""
 
     def __init__(self, opgraph, stream, graph, tensors, semantics=None, plan_chunk=512, warmup=2,
-                 softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None, fp8_rows=False):
+                 softmax_shift=None, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None, fp8_rows=False,
+                 edge_mm_gather=False):
         if graph.device.type != "cuda":
             raise RuntimeError("GraphedRun captures device launches: the graph must be on a HIP device")
         self.tensors = tensors
@@ -1916,7 +1961,7 @@ class GraphedRun:
             for _ in range(max(1, warmup)):
                 Executor(opgraph, stream, graph, tensors, semantics, plan_chunk, softmax_shift=softmax_shift,
                          gather_dtype=gather_dtype, multi_reduce_blocked=multi_reduce_blocked,
-                         mm_precision=mm_precision, fp8_rows=fp8_rows).run()
+                         mm_precision=mm_precision, fp8_rows=fp8_rows, edge_mm_gather=edge_mm_gather).run()
         torch.cuda.current_stream(graph.device).wait_stream(side)
         torch.cuda.synchronize(graph.device)
         self.cuda_graph = torch.cuda.CUDAGraph()
@@ -1927,7 +1972,7 @@ class GraphedRun:
                 self.executor = Executor(opgraph, stream, graph, tensors, semantics, plan_chunk,
                                          softmax_shift=softmax_shift, gather_dtype=gather_dtype,
                                          multi_reduce_blocked=multi_reduce_blocked, mm_precision=mm_precision,
-                                         fp8_rows=fp8_rows)
+                                         fp8_rows=fp8_rows, edge_mm_gather=edge_mm_gather)
                 self.outputs = self.executor.run()
         finally:
             taken, ops._CAPTURED_WT[:] = list(ops._CAPTURED_WT), []

@@ -440,6 +440,55 @@ def aggregate_expr(graph, shape, operands, bins, sfs=None, swap=False, plan=None
     return out
 
 
+# (nnz, N, device, stream) -> the slab of gta_aggregate_edge_mm.  Every call overwrites what it reads, so calls
+# on one stream share a slab; a slab is allocated and used on its key's stream alone, so dropping an
+# entry that a queued launch still reads is safe (the caching allocator reuses it on that stream only)
+_EMM_WS = {}
+
+
+def aggregate_edge_mm(graph, ef, w, p=None, q=None, sf=None, out=None):
+    """y[i] = sum_{e in row i} sf(ef[e] . w + p[src(e)] + q[i]) in one pass (gta_aggregate_edge_mm: the
+    edge GEMM and the expression gather fused; the [E, N] product never reaches HBM).  ef fp32
+    [nnz, K] in CSR edge order, w fp32 [K, N] (its transpose cached as update_mm caches it), p fp32
+    [n_cols, N] or None, q fp32 [n_rows, N] or None.  Within the fp32 bound of the unfused pair
+    (update_mm, then aggregate_expr), not its bits; two calls give the same bits.  Returns None for a
+    shape the kernel does not take (GTA_ERR_UNSUPPORTED: N not 64 / 128, K < 32, rows not 16-B
+    aligned): run the ops unfused."""
+    _need_gpu(graph.indptr, ef, w, p, q, out)
+    K, N = w.shape
+    ldef = _rows(ef, "ef")
+    _rows(w, "w")
+    if ef.shape[1] != K or ef.shape[0] < graph.nnz:
+        raise ValueError(f"aggregate_edge_mm: ef must be [nnz >= {graph.nnz}, {K}], got {tuple(ef.shape)}")
+    for t, name, need in ((p, "p", graph.n_cols), (q, "q", graph.n_rows)):
+        if t is not None and (t.shape[1] != N or t.shape[0] < need):
+            raise ValueError(f"aggregate_edge_mm: {name} must be [>= {need}, {N}], got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty(graph.n_rows, N, dtype=torch.float32, device=ef.device)
+    elif out.shape != (graph.n_rows, N):
+        raise ValueError(f"aggregate_edge_mm: out must be [{graph.n_rows}, {N}]")
+    ldy = _rows(out, "out")
+    wt = _transposed(w)
+    nb = check(_L().gta_aggregate_edge_mm_workspace_bytes(graph.nnz, N), "aggregate_edge_mm_workspace_bytes")
+    capturing = ef.is_cuda and torch.cuda.is_current_stream_capturing()
+    key = (graph.nnz, N, ef.device, _stream(ef.device))
+    ws = None if capturing else _EMM_WS.get(key)
+    if ws is None:
+        ws = torch.empty(max(1, nb // 4), dtype=torch.float32, device=ef.device)
+        if not capturing:  # (a capture's slab belongs to the graph's private pool)
+            if len(_EMM_WS) >= 16:
+                _EMM_WS.pop(next(iter(_EMM_WS)))  # the oldest entry
+            _EMM_WS[key] = ws
+    rc = _L().gta_aggregate_edge_mm(_ptr(graph.indptr), _ptr(graph.indices), graph.n_rows, graph.nnz, _ptr(ef), ldef, K,
+                                    _ptr(wt), _rows(wt, "w^T"), N, _lib.GTA_F32, _ptr(p), 0 if p is None else _rows(p, "p"),
+                                    _ptr(q), 0 if q is None else _rows(q, "q"), _sf(sf), _ptr(out), ldy, _ptr(ws),
+                                    _stream(ef.device))
+    if rc == _lib.ERR_UNSUPPORTED:
+        return None
+    check(rc, "aggregate_edge_mm")
+    return out
+
+
 class BlockedPlan:
     """Column-blocked aggregate plan (gta_aggregate_blocked_plan_build): per-row segment table over
     B source-column blocks, heaviest-first row order, and the work items -- every (block, row)

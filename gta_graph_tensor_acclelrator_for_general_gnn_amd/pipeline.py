@@ -20,7 +20,7 @@ class Layer:
     def __init__(self, network, layer, graph, feature, reorder=False, heads=16, candidate=0, tile_start=None,
                  op_array=None, tile_size_list=None, metadata=None, pingpang=True, sinput=False, aggregator="ADD",
                  stable_softmax=False, gather_dtype=None, multi_reduce_blocked=False, mm_precision=None,
-                 fp8_rows=False):
+                 fp8_rows=False, edge_mm_gather=False):
         """pingpang / sinput: compile()'s isPingpang / isSinput (code/compiler.py:475-510) for the
         fusion search; the reference's start.py passes its command-line flags through.
         aggregator: the message gathers' reduce function, "ADD" / "MAX" / "MIN" / "MEAN" / "VAR" /
@@ -43,7 +43,9 @@ class Layer:
         fp32 MM through ops.update_mm(precision="bf16x3") (Executor.mm_precision).
         fp8_rows: False (the default: nothing changes) or True -- under gather_dtype e4m3, run() also
         gathers the tables of its row-chunked ADD aggregates (narrow rows: GIN products' F = 100) as
-        e4m3 rows on whole 128-B lines (Executor.fp8_rows)."""
+        e4m3 rows on whole 128-B lines (Executor.fp8_rows).
+        edge_mm_gather: False (the default: nothing changes) or True -- run() sends PNA's edge MM, ADDs,
+        SF and gather through one ops.aggregate_edge_mm launch (Executor.edge_mm_gather)."""
         if mm_precision not in (None, "f32", "bf16x3"):
             raise ValueError(f"mm_precision: None, 'f32' or 'bf16x3', not {mm_precision!r}")
         self.mm_precision = None if mm_precision == "f32" else mm_precision
@@ -58,6 +60,7 @@ class Layer:
             else bool(stable_softmax)
         self.multi_reduce_blocked = bool(multi_reduce_blocked)
         self.fp8_rows = bool(fp8_rows)
+        self.edge_mm_gather = bool(edge_mm_gather)
         self.graph = graph
         self.records = frontend.gen_ops(network, layer, graph.n_rows, graph.nnz, feature, reorder, heads, aggregator)
         self.sem = Semantics.for_network(network, reorder, clones=frontend.pna_clones(len(aggregator)) if multi else None)
@@ -122,6 +125,8 @@ class Layer:
             opts["mm_precision"] = self.mm_precision
         if self.fp8_rows:
             opts["fp8_rows"] = True
+        if self.edge_mm_gather:
+            opts["edge_mm_gather"] = True
         res, ex = executor.run_stream(self.opgraph, self.stream, self.graph, tensors, self.sem, plan_chunk, sync=sync,
                                       **opts)
         if model:

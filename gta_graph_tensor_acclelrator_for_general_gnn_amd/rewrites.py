@@ -284,3 +284,25 @@ def edge_expr(g, cons, sem, softmax, attn, pushdown, gacc):
             continue
         found[G.idx] = e
     return found
+
+
+def edge_mm_gather(g, cons, expr):
+    """{gather G: (k, MM op)} for every edge_expr plan that gta_aggregate_edge_mm's form covers: shape
+    1 or 2 with every bin ADD and no SF on the inner op, no pushed-down leaf, and exactly one leaf --
+    leaves[k] -- an applyedge MM that only the tree reads and that multiplies an edge input, not an
+    op's output (PNA op 2).  What the other leaves are is known only once they are evaluated."""
+    found = {}
+    for G, e in expr.items():
+        if e["shape"] not in (1, 2) or any(b != "ADD" for b in e["bins"]) or (e["shape"] == 2 and e["sfs"][0] is not None):
+            continue
+        if any(ref[0] == "pmm" for ref in e["leaves"]):
+            continue
+        hits = []
+        for k, (op, slot) in enumerate(e["leaves"]):
+            src = g.inputs[op][slot]
+            m = g.ops[src.op] if src.kind == "op" else None
+            if m is not None and m.type == "applyedge" and m.comp == "MM" and cons[m.idx] == [op] and not op_inputs(g, m.idx):
+                hits.append((k, m.idx))
+        if len(hits) == 1:
+            found[G] = hits[0]
+    return found

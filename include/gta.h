@@ -65,7 +65,9 @@ extern "C" {
                               (gta_gat_aggregate_blocked_online and its workspace size; no existing
                               signature changes);
                               15 (additive): GTA_FP8 rows in gta_aggregate / gta_aggregate_self (the
-                              row-chunked form; no new symbol, no signature changes) */
+                              row-chunked form; no new symbol, no signature changes);
+                              15 (additive): gta_aggregate_edge_mm and its workspace size (the edge GEMM
+                              fused with its gather; no existing signature changes) */
 
 /* status codes */
 enum { GTA_OK = 0, GTA_ERR_ARG = -1, GTA_ERR_HIP = -2, GTA_ERR_UNSUPPORTED = -3 };
@@ -718,6 +720,38 @@ int gta_update_mlp(const void* x, int64_t ldx, int64_t M, int64_t K1, const void
 int gta_update_mm_t_split(const void* x, int64_t ldx, const int32_t* row_idx, int64_t M, int64_t K, const void* wt,
                           int64_t ldwt, int64_t N, int dtype, int sf, float* out, int64_t ldo, int64_t splits,
                           void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- Fused edge GEMM + gather (ABI 15 additive): PNA's applyedge MM, ADDs, SF and gather R ----
+ *   y[i, :] = sum_{e in row i} sf( ef[e, :] . W  +  p[indices[e], :]  +  q[i, :] )
+ * in one pass over the edges (k_emm_gather) and a short pass over the rows (k_emm_finish): the
+ * [nnz, N] product that gta_update_mm_t would store and gta_aggregate_expr read back never exists.
+ * Reference: the fused [applyedge, gather] (MM, ADD) instruction; PNA ops 2, 5-8 of
+ * vTCAD/GraphOP/genGraphOP.py.
+ * Operands: ef [nnz, K] fp32 in CSR edge order (ldef >= K, rows 4-B aligned); wt = W^T [N, K] as
+ * gta_update_mm_t takes it; p [n_cols, N] read at indices[e], or NULL; q [n_rows, N] read at the
+ * edge's destination row, or NULL; y [n_rows, N] fp32.
+ * Per edge and column: m = (ef[e, :] . W)[c] contracted in gta_update_mm_t's GTA_F32 k order;
+ * z = fl(m + fl(p + q)), or fl(m + p) / fl(m + q) / m when an operand is NULL; t = sf(z),
+ * any GTA_SF_*.  Each step is an fp32 value exactly as the unfused ops store it (no contraction).
+ * Row sum: a row without edges is 0.0f (from its degree, not sf(0)).  The CSR's edges are cut into
+ * segments of S = 32 consecutive edges, whatever their rows.  Inside a segment a row's edges are
+ * added one by one in edge order, starting from 0.0f; a row that lies inside one segment is that
+ * sum.  A row that spans segments s0 < s1 is ((P[s0] + P[s0 + 1]) + ...) + P[s1], P[s] its sum
+ * inside segment s.  No atomics: two calls are bitwise equal, and the result depends only on the
+ * CSR and the operands.  It is within the fp32 summation bound of the fp64 value but NOT promised
+ * bitwise equal to the unfused pair (whose sum order follows the aggregate's plan).
+ * Supported: dtype GTA_F32, N 64 or 128, K >= 32, 16-B aligned rows of wt (ldwt % 4 == 0), y, p and
+ * q; anything else GTA_ERR_UNSUPPORTED (GTA_F32_BF16X3 is a stated follow-up).  NULL indptr / y, or
+ * with nnz > 0 NULL indices / ef / wt / workspace, a row stride below its width, a bad dtype or sf:
+ * GTA_ERR_ARG.  Both are decided before any device work, y untouched.  nnz == 0: y all zero; ef,
+ * indices, p and q are never read.  n_rows == 0 returns GTA_OK.
+ * workspace: gta_aggregate_edge_mm_workspace_bytes = ceil(nnz / S) x 2 x N floats (per segment, the
+ * partial of the row cut at its start and of the row cut at its end); < 0 on bad sizes. */
+int64_t gta_aggregate_edge_mm_workspace_bytes(int64_t nnz, int64_t N);
+int gta_aggregate_edge_mm(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t nnz,
+                          const float* ef, int64_t ldef, int64_t K, const void* wt, int64_t ldwt, int64_t N,
+                          int dtype, const float* p, int64_t ldp, const float* q, int64_t ldq, int sf,
+                          float* y, int64_t ldy, void* workspace, void* stream);
 
 /* ---- f2 TILE-NNZ metadata ----------------------------------------------
  * counts[t, j] = #{ distinct (dst, j) : dst in [t*T, (t+1)*T), an edge dst <- j, dst != j }

@@ -11,7 +11,7 @@ sys.path.insert(0, ROOT)
 from gta_graph_tensor_acclelrator_for_general_gnn_amd import configs, executor  # noqa: E402
 
 
-def main(names=None, reps=5, trace=False, graphed=False, gather_dtype=None, fp8_rows=False):
+def main(names=None, reps=5, trace=False, graphed=False, gather_dtype=None, fp8_rows=False, edge_mm_gather=False):
     dev = torch.device("cuda:0")
     out = {}
     for name in (names or list(configs.CONFIGS)):
@@ -21,6 +21,7 @@ def main(names=None, reps=5, trace=False, graphed=False, gather_dtype=None, fp8_
         for lay in layers:  # --gather-dtype bf16: the blocked aggregates' tables stored as bf16 (Layer.gather_dtype)
             lay.gather_dtype = gather_dtype
             lay.fp8_rows = fp8_rows  # --fp8-rows: with fp8, the row-chunked aggregates gather e4m3 rows too
+            lay.edge_mm_gather = edge_mm_gather  # --edge-mm-gather: PNA's edge MM fused with its gather
         times = []
         nrep = reps if g.nnz > 10 ** 6 else 10 * reps  # small graphs: launch-bound, more samples
         for r in range(nrep + 1):
@@ -43,7 +44,7 @@ def main(names=None, reps=5, trace=False, graphed=False, gather_dtype=None, fp8_
                 if prev is not None:
                     t["x"] = prev  # layer k reads layer k-1's (static) graph output
                 runs.append(executor.GraphedRun(lay.opgraph, lay.stream, g, t, lay.sem, gather_dtype=gather_dtype,
-                                                fp8_rows=fp8_rows))
+                                                fp8_rows=fp8_rows, edge_mm_gather=edge_mm_gather))
                 prev = runs[-1].outputs[sorted(runs[-1].outputs)[-1]]
             gt = []
             for r in range(reps + 1):
@@ -63,7 +64,8 @@ def main(names=None, reps=5, trace=False, graphed=False, gather_dtype=None, fp8_
                 if x is not None:
                     t["x"] = x
                 res, ex = executor.run_stream(lay.opgraph, lay.stream, g, t, lay.sem, trace=True,
-                                              gather_dtype=gather_dtype, fp8_rows=fp8_rows)
+                                              gather_dtype=gather_dtype, fp8_rows=fp8_rows,
+                                              edge_mm_gather=edge_mm_gather)
                 events += ex.trace_events
                 x = res.outputs[sorted(res.outputs)[-1]]
             executor.save_chrome_trace(events, os.path.join(ROOT, "gpurun_out", f"trace_{name}.json"))
@@ -86,7 +88,7 @@ if __name__ == "__main__":
         online = True
     argv = [a for a in sys.argv[1:] if a not in ("--trace", "--hipgraph", "--no-mlp", "--graph-all", "--no-bf16-sum",
                                                  "--no-edge-flat", "--no-edge-expr", "--stable-softmax", "--no-auto-graph",
-                                                 "--fp8-rows")]
+                                                 "--fp8-rows", "--edge-mm-gather")]
     if "--no-auto-graph" in sys.argv[1:]:  # every forward through the executor itself (its host time included), no replay
         executor.set_auto_graph(False)
     if "--stable-softmax" in sys.argv[1:]:  # the GAT softmax chains shifted by their row maxima (A/B of the shift pass)
@@ -111,4 +113,4 @@ if __name__ == "__main__":
         ops.MM_ROWS_MIN_M = int(argv[i + 1])
         del argv[i:i + 2]
     main(argv or None, trace="--trace" in sys.argv[1:], graphed="--hipgraph" in sys.argv[1:], gather_dtype=gdt,
-         fp8_rows="--fp8-rows" in sys.argv[1:])
+         fp8_rows="--fp8-rows" in sys.argv[1:], edge_mm_gather="--edge-mm-gather" in sys.argv[1:])
